@@ -6,6 +6,13 @@ profile + 128-bin DM rows, plus HBM GB/s vs peak.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--n ROWS_PER_GPU]
                   [--path lyon8|bates22|subband|all30|pfd|pfd22] [--option NAME=VALUE ...]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (the contract
+fields and the roofline of the timed steps themselves).  --dump-outputs DIR then writes what
+the last timed step computed as DIR/<name>.npy (float64; a fixed, seeded sample of the rows
+when the arrays are large; the inputs are seeded, so two builds compare output for output).
+--full adds everything that takes runs of its own: the CPU baselines and the extra configs.
 
 One "step" = one pass of the hot path (pfe_lyon8_u8 through the C-ABI, device pointers,
 inputs resident in HBM) over the rank's whole batch of synthetic candidates (config 2:
@@ -14,7 +21,7 @@ torch.distributed.run; candidates shard with no data-path collective (weak scali
 10M rows per rank); the timed region is bracketed by barrier + synchronize and the MAX over
 ranks is reported; value = all rows processed by all ranks / that time.
 
-Besides the contract fields the JSON line carries:
+Besides the contract fields the JSON line carries (cpu_baseline and extra with --full only):
   roofline     : the lyon8 kernel's algorithmic bytes per launch (n * (lp + ld + 64) B)
                  / its average duration, measured with HIP events on the stream the kernel
                  runs on, against the 8.0 TB/s HBM3E peak; traffic = PMC-measured HBM bytes
@@ -22,7 +29,7 @@ Besides the contract fields the JSON line carries:
   cpu_baseline : the reference-equivalent per-candidate numpy/scipy loop (oracle.lyon.lyon8,
                  the scalar port of PHCXFile.py:320-379) timed on this host, 1 core, on a
                  bounded sample of the same synthetic rows (rank 0, N=1 only)
-  extra        : (--no-extra skips it) the other BASELINE configs, each with its own
+  extra        : (--full; --no-extra skips it) the other BASELINE configs, each with its own
                  roofline and CPU baseline:
                    config5 -- (every N) BASELINE config 5's shard: 10M candidates per GPU,
                               8 Lyon + 22 Bates features into one (n, 30) matrix, then the
@@ -83,10 +90,18 @@ def parse():
     ap.add_argument("--pfd-shape", default="16x32x128", help="npart x nsub x proflen (pfd path)")
     ap.add_argument("--cpu-sample", type=int, default=None,
                     help="rows for the CPU baseline sample (0 disables)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run what takes runs of its own: the CPU "
+                         "baselines and (lyon8 path) the extra configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy "
+                         "(float64; a fixed seeded sample of the rows, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
     ap.add_argument("--no-cpu-multicore", action="store_true",
-                    help="skip the multi-process CPU baseline of the 22-score paths")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra configs (N=1 lyon8)")
+                    help="with --full: skip the multi-process CPU baseline of the 22-score paths")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the extra configs (lyon8 path)")
     ap.add_argument("--config5-n", type=int, default=10_000_000,
                     help="candidates per GPU of the extra config-5 line (BASELINE: 10M)")
     ap.add_argument("--gather", action="store_true",
@@ -357,6 +372,7 @@ class Ctx:
         torch.cuda.set_stream(self.stream)
         self.eng.set_stream(self.stream.cuda_stream)
         self.dev = f"cuda:{local}"
+        self.outputs = {}  # name -> what the timed path's caller receives (--dump-outputs)
 
     def barrier(self):
         if self.dist_on:
@@ -431,6 +447,31 @@ def common_fields(ctx, n, steps, warmup, elapsed):
     }
 
 
+DUMP_BUDGET = 48 << 20  # bytes of float64 over all the dumped arrays (the limit is 64 MB)
+
+
+def dump_outputs(ctx, dirname):
+    """Write the arrays of ctx.outputs (what the last timed step handed its caller) as
+    dirname/<name>.npy in float64.  When they exceed DUMP_BUDGET, the same seeded sample of
+    the rows (first and last row included, in row order) is taken from every array."""
+    import numpy as np
+
+    torch = ctx.torch
+    torch.cuda.synchronize()
+    os.makedirs(dirname, exist_ok=True)
+    n = min(int(t.shape[0]) for t in ctx.outputs.values())
+    row_bytes = sum(8 * (t.numel() // max(1, int(t.shape[0]))) for t in ctx.outputs.values())
+    keep = max(2, DUMP_BUDGET // max(1, row_bytes))
+    idx = None
+    if n > keep:
+        pick = np.random.default_rng(20261031).choice(n, size=keep - 2, replace=False)
+        idx = torch.from_numpy(np.unique(np.concatenate([pick, [0, n - 1]]))).to(ctx.dev)
+    for name, t in ctx.outputs.items():
+        rows = t if idx is None else t.index_select(0, idx)
+        np.save(os.path.join(dirname, name + ".npy"),
+                np.ascontiguousarray(rows.cpu().numpy().astype(np.float64)))
+
+
 # ---- paths ------------------------------------------------------------------------------
 def run_lyon8(ctx, args, n, lp):
     from pulsarfeatureextractor_amd.synth import lyon_batch_torch
@@ -443,6 +484,7 @@ def run_lyon8(ctx, args, n, lp):
         ctx.eng.lyon8(prof, dm, out=out)
 
     elapsed, kern_ms, kern_max = ctx.time_steps(step, args.steps, args.warmup)
+    ctx.outputs = {"features": out}
     bytes_per_launch = n * (lp + args.ld + 8 * 8)
     achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
     # HBM bytes per launch: the latest round's PMC passes of this command at the current defaults
@@ -569,6 +611,7 @@ def run_bates22(ctx, args, n, lp, steps, warmup, small_warm=False):
                             out=out[:m], status=status[:m])
 
     elapsed, kern_ms, kern_max = ctx.time_steps(step, steps, warmup, warm)
+    ctx.outputs = {"scores": out, "status": status}
     res = {
         "metric": f"candidates/sec (22-score path, {lp}-bin)",
         **common_fields(ctx, n, steps, warmup, elapsed),
@@ -598,6 +641,7 @@ def run_subband(ctx, args, n, lsb, steps, warmup):
         ctx.eng.subband3(bt["prof"], bt["sub"], bt["scal"], out=out, status=status)
 
     elapsed, kern_ms, kern_max = ctx.time_steps(step, steps, warmup)
+    ctx.outputs = {"scores": out, "status": status}
     # one read of the profile, the sub-bands and the width, one write of 3 scores + status
     per_cand = lsb + 16 * lsb + 8 + 3 * 8 + 4
     achieved = per_cand * n / (kern_ms * 1e-3) / 1e9
@@ -836,17 +880,26 @@ def main():
     ctx = Ctx(args)
     torch = ctx.torch
     n = args.n
-    want_cpu = ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline and args.cpu_sample > 0
+    full = args.full  # a plain run: the timed steps, the dump and the result line only
+    want_cpu = (full and ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline
+                and args.cpu_sample > 0)
+    want_extra = full and not args.no_extra
+
+    def dump():  # right after the timed steps, before anything else reuses the memory
+        if args.dump_outputs and ctx.rank == 0:
+            dump_outputs(ctx, args.dump_outputs)
+        ctx.outputs = {}
 
     out = None
     if args.path == "lyon8":
         result, out = run_lyon8(ctx, args, n, lp)
+        dump()
         if want_cpu:
             result["cpu_baseline"] = cpu_baseline_lyon8(lp, args.ld, args.cpu_sample)
             omp = cpu_baseline_lyon8_omp(lp, args.ld)
             if omp is not None:
                 result["cpu_baseline_multicore"] = omp
-        if not args.no_extra:
+        if want_extra:
             extra = {}
             if not args.gather:
                 del out
@@ -854,10 +907,11 @@ def main():
             torch.cuda.empty_cache()
             extra["config5"] = run_config5(ctx, args, n=args.config5_n)
             result["extra"] = extra
-        if ctx.world == 1 and not args.no_extra:
+        if ctx.world == 1 and want_extra:
             # config 3 at the 10M rows BASELINE names: 2 timed steps of ~15 s
             r3, o3 = run_bates22(ctx, args, 10_000_000, 128, steps=2, warmup=0, small_warm=True)
             r3["tiles_identical"] = tiles_identical(ctx, o3, r3.pop("_status"))
+            ctx.outputs = {}
             del o3
             torch.cuda.empty_cache()
             if not args.no_cpu_baseline:
@@ -866,6 +920,7 @@ def main():
                     r3["cpu_baseline_multicore"] = cpu_baseline_bates22_mp(128)
             extra["config3"] = r3
             r4, o4 = run_subband(ctx, args, 1_000_000, 256, steps=20, warmup=3)
+            ctx.outputs = {}
             del o4
             torch.cuda.empty_cache()
             if not args.no_cpu_baseline:
@@ -883,12 +938,14 @@ def main():
             extra["lyon8_phcx_ndm100"] = run_lyon8_phcx(ctx, args, ld=12800)
     elif args.path == "bates22":
         result, out = run_bates22(ctx, args, n, lp, args.steps, args.warmup)
+        dump()
         if want_cpu:
             result["cpu_baseline"] = cpu_baseline_bates22(lp, args.cpu_sample)
             if not args.no_cpu_multicore:
                 result["cpu_baseline_multicore"] = cpu_baseline_bates22_mp(lp)
     elif args.path == "subband":
         result, out = run_subband(ctx, args, n, lp, args.steps, args.warmup)
+        dump()
         if want_cpu:
             result["cpu_baseline"] = cpu_baseline_subband(lp, args.cpu_sample)
     elif args.path == "all30":
@@ -904,6 +961,7 @@ def main():
             ctx.eng.features30(bt["prof"], dmrows, bt["sub"], bt["dmcurve"], bt["scal"], out=out)
 
         elapsed, kern_ms, kern_max = ctx.time_steps(step, args.steps, args.warmup)
+        ctx.outputs = {"features": out}
         result = {
             "metric": "candidates/sec (8+22-feature path, 128-bin)",
             **common_fields(ctx, n, args.steps, args.warmup, elapsed),
@@ -918,6 +976,7 @@ def main():
             },
             "roofline": bates_roofline(n, kern_ms, kern_max, "pfe_lyon8_u8 + pfe_bates22, one step"),
         }
+        dump()
         if want_cpu:
             b = cpu_baseline_bates22(lp, args.cpu_sample)
             l8 = cpu_baseline_lyon8(lp, args.ld, 8000)
@@ -954,6 +1013,7 @@ def main():
 
             elapsed, kern_ms, kern_max = ctx.time_steps(step, args.steps, args.warmup)
             out = holder["r"]["lyon8"]
+            ctx.outputs = {"features": out, "status": holder["r"]["status"]}
             bytes_per_launch = n * (npart * nsub * L * 8 + nsub * 8 + 8 * 8 + 8 * 8 + 4)
             achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
             result = {
@@ -970,6 +1030,7 @@ def main():
                              "algorithmic_bytes_per_launch": bytes_per_launch,
                              "avg_kernel_ms": kern_ms, "avg_kernel_ms_max_over_ranks": kern_max},
             }
+            dump()
             if want_cpu:
                 result["cpu_baseline"] = cpu_baseline_pfd(pfd_shape, args.cpu_sample)
         else:
@@ -980,6 +1041,7 @@ def main():
                 ctx.eng.pfd_bates22(tp, tf, ts, out=out, status=status)
 
             elapsed, kern_ms, kern_max = ctx.time_steps(step, args.steps, args.warmup)
+            ctx.outputs = {"scores": out, "status": status}
             # 0 (no frozen count for this fold shape): no roofline fraction, never the PHCX count
             ops = (load_ops_per_candidate("r03_pfd22_ops.json")
                    if pfd_shape == (16, 32, 128) else None) or 0
@@ -999,6 +1061,7 @@ def main():
                                        f"(pfe_pfd_bates22)", **common_cfg},
                 "roofline": roof,
             }
+            dump()
             if want_cpu:
                 result["cpu_baseline"] = cpu_baseline_pfd22(pfd_shape, args.cpu_sample)
     if args.gather and ctx.dist_on and out is not None:

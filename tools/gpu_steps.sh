@@ -8,7 +8,7 @@
 # TAG defaults to r06.  A/B of library builds: tools/ab.sh.  Steps:
 #   suite        pytest -m gpu (whole GPU suite)
 #   smoke        __graft_entry__.smoke()
-#   bench        bench.py --gpus 1 (the default bench line, all extras)
+#   bench        bench.py --gpus 1 --full (the bench line with the CPU baselines and all extras)
 #   trace_l8     rocprofv3 kernel trace of the headline Lyon-8 kernel (bench.py, no extras)
 #   pmc_l8       FETCH_SIZE and WRITE_SIZE passes of the same command (one pass each)
 #   trace_b22    rocprofv3 kernel trace of the 22-score chain, groups serialised
@@ -44,7 +44,7 @@ for step in "$@"; do
       timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > $O/${T}_smoke.txt 2>&1 \
         || fail smoke $O/${T}_smoke.txt ;;
     bench)
-      timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench_default.json \
+      timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${T}_bench_default.json \
         2> $O/${T}_bench_default.err || fail bench $O/${T}_bench_default.err ;;
     trace_l8)
       timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof_l8 -o trace -- \

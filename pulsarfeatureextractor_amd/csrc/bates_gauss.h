@@ -723,7 +723,7 @@ __device__ HistFit fit_gaussian_hist_wide(const WideHist& w, double* scr, int la
     p[0] = s0;
     p[1] = mu0;
     p[2] = a0;
-    lmdif_g<3>(fn, p, 200 * 4, rs);
+    lmdif_mem<3>(fn, p, 200 * 4, rs);
     double cs = 0.0;
     for (int k = 0; k < nsl; ++k) {
       const int i = lane + 64 * k;
@@ -833,7 +833,7 @@ __global__ __launch_bounds__(64) void k_ghist_wide(BatesArgs a) {
         if (i < hb) qq += (fx.w.y(i) - mean) * (fx.w.y(i) - mean);
       }
       double pf[2] = {sqrt(wsum(qq) / (double)hb), cmax};
-      lmdif_g<2>(fx, pf, 200 * 3, RowStore<2>{scr, nsl});
+      lmdif_mem<2>(fx, pf, 200 * 3, RowStore<2>{scr, nsl});
       const MeanStd ms = ghist_meanstd<P, F>(g, a.lp, stage);
       if (lane == 0) {
         double* o = a.out + c * 22;

@@ -15,8 +15,14 @@
 //
 // Between phases the per-fit state lives in LDS, structure-of-arrays ([element][fit]), so the
 // SIMT phase reads it conflict-free and the m-phase reads one fit's values as broadcasts.
-// The arithmetic is that of lmdif in lm_wave.h operation for operation (and thus of MINPACK,
-// up to the tree-ordered m-sums), so results are bit-identical to the wave-per-fit solver.
+// The operations are those of lmdif in lm_wave.h (and thus of MINPACK, up to the tree-ordered
+// m-sums).
+// Q^T f here is contracted and lmdif's is not, so results are bit-identical to the
+// wave-per-fit solver only in PFE_LA_NOFMA builds, and agree to the last bits otherwise
+// (test_batched_solver_matches_wave_solver).
+//
+// The step rule and info tests of a trial are lm_wave.h's scalar core; the in-place scaling
+// after qrfac (blm_scaling) is shared with the pooled engine of lm_group.h.
 #pragma once
 
 #include <type_traits>
@@ -82,14 +88,33 @@ __device__ __forceinline__ void blm_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The scaling MINPACK updates after qrfac, in place (shared with lm_group.h): diag of fit f
+// (first iteration: from the column norms, with xnorm and delta -> S; later: the running
+// maximum kept in S).  lane: this lane's index among the lanes that work on the fit.
+template <int N, int FPW>
+__device__ __forceinline__ void blm_scaling(BlmState<N, FPW>& S, int f, int iter, int lane,
+                                            const double (&acn)[N], const double (&x)[N],
+                                            double (&diag)[N]) {
+  if (iter == 1) {
+    double xnorm, delta;
+    lm_init_scaling(acn, x, diag, xnorm, delta);
+    if (lane == 0) {
+      S.xnorm[f] = xnorm;
+      S.delta[f] = delta;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < N; ++j) diag[j] = S.diag[j][f];
+  }
+}
+
 // The outer-iteration body of lmdif for fit f (m-phase): forward-difference Jacobian at
-// S.x[.][f] with residuals fvec, QR, (first iteration: diag, xnorm, delta), Q^T f, R, gnorm,
-// the gtol test and the diag update.  Writes everything the SIMT phase needs.
+// S.x[.][f] with residuals fvec, QR, (first iteration: diag, xnorm, delta), Q^T f, R, the
+// diag update.  Writes everything the SIMT phase needs.
 template <int N, int MPL, int FPW, class Fn>
 __device__ __forceinline__ void blm_outer(const Fn& fcn, const double (&fvec)[MPL],
                                           const typename FnCache<Fn>::type& cache, double fnorm,
                                           int f, BlmState<N, FPW>& S, int iter, int nfev) {
-  const double eps = 1.4901161193847656e-08;  // sqrt(max(epsfcn, epsmch)) = 2^-26
   const int lane = lane_id();
   LM_ADD(1, 1);
   LM_T0(t_fd);
@@ -100,8 +125,7 @@ __device__ __forceinline__ void blm_outer(const Fn& fcn, const double (&fvec)[MP
 #pragma unroll
   for (int j = 0; j < N; ++j) {
     const double temp = x[j];
-    double h = eps * fabs(temp);
-    if (h == 0.0) h = eps;
+    const double h = lm_fd_step(temp);
     x[j] = temp + h;
     fn_eval_col<Fn, N, MPL>(fcn, x, j, temp, wa4, cache);
     x[j] = temp;
@@ -117,29 +141,9 @@ __device__ __forceinline__ void blm_outer(const Fn& fcn, const double (&fvec)[MP
   qrfac<N, MPL>(fjac, ipvt, rdiag, acn);
   LM_T0(t_qt);
   LM_ADD(6, t_qt - t_qr);
-  double diag[N];
-  if (iter == 1) {
-    double wa3[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      diag[j] = acn[j];
-      if (acn[j] == 0.0) diag[j] = 1.0;
-    }
-#pragma unroll
-    for (int j = 0; j < N; ++j) wa3[j] = diag[j] * x[j];
-    const double xnorm = enorm_u(wa3);
-    double delta = LM_FACTOR * xnorm;
-    if (delta == 0.0) delta = LM_FACTOR;
-    if (lane == 0) {
-      S.xnorm[f] = xnorm;
-      S.delta[f] = delta;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < N; ++j) diag[j] = S.diag[j][f];
-  }
+  double diag[N], qtf[N];
+  blm_scaling(S, f, iter, lane, acn, x, diag);
   // (Q^T) fvec -> qtf; restore the diagonal of R
-  double qtf[N];
 #pragma unroll
   for (int k = 0; k < MPL; ++k) wa4[k] = fvec[k];
   {
@@ -168,7 +172,6 @@ __device__ __forceinline__ void blm_outer(const Fn& fcn, const double (&fvec)[MP
     if (lane <= j) S.r[tri_idx(0, j) + lane][f] = fjac[0][j];
   // the scaled gradient norm and the gtol test run in the next SIMT phase (blm_simt), one
   // fit per lane, from R, qtf, acnorm and ipvt in LDS; info = -1 marks "not yet tested"
-  const int info = -1;
   if (lane == 0) {
 #pragma unroll
     for (int j = 0; j < N; ++j) {
@@ -177,7 +180,7 @@ __device__ __forceinline__ void blm_outer(const Fn& fcn, const double (&fvec)[MP
       S.acn[j][f] = acn[j];
       S.ipvt[j][f] = ipvt[j];
     }
-    S.info[f] = info;
+    S.info[f] = -1;
     S.nfev[f] = nfev;
     S.iter[f] = iter;
     S.fnorm[f] = fnorm;
@@ -316,24 +319,8 @@ __device__ __forceinline__ void blm_trial(const Fn& fcn, int f, BlmState<N, FPW>
   const double pnorm = S.pnorm[f], prered = S.prered[f], dirder = S.dirder[f];
   const double gnorm = S.gnorm[f];
   int iter = S.iter[f];
-  double actred = -1.0;
-  if (0.1 * fnorm1 < fnorm) {
-    const double q = fnorm1 / fnorm;
-    actred = 1.0 - q * q;
-  }
-  double temp = S.tstale[f];
-  double ratio = 0.0;
-  if (prered != 0.0) ratio = actred / prered;
-  if (ratio <= 0.25) {
-    if (actred >= 0.0) temp = 0.5;
-    if (actred < 0.0) temp = 0.5 * dirder / (dirder + 0.5 * actred);
-    if (0.1 * fnorm1 >= fnorm || temp < 0.1) temp = 0.1;
-    delta = temp * fmin(delta, pnorm / 0.1);
-    par = par / temp;
-  } else if (par == 0.0 || ratio >= 0.75) {
-    delta = pnorm / 0.5;
-    par = 0.5 * par;
-  }
+  const LMStep st = lm_step_rule(fnorm1, fnorm, pnorm, prered, dirder, S.tstale[f], delta, par);
+  const double actred = st.actred, ratio = st.ratio;
   const bool accepted = ratio >= 1e-4;
   if (accepted) {
     double wa3[N];
@@ -343,16 +330,7 @@ __device__ __forceinline__ void blm_trial(const Fn& fcn, int f, BlmState<N, FPW>
     fnorm = fnorm1;
     ++iter;
   }
-  int info = 0;
-  if (fabs(actred) <= LM_FTOL && prered <= LM_FTOL && 0.5 * ratio <= 1.0) info = 1;
-  if (delta <= LM_XTOL * xnorm) info = 2;
-  if (fabs(actred) <= LM_FTOL && prered <= LM_FTOL && 0.5 * ratio <= 1.0 && info == 2) info = 3;
-  if (info == 0) {
-    if (nfev >= maxfev) info = 5;
-    if (fabs(actred) <= EPSMCH && prered <= EPSMCH && 0.5 * ratio <= 1.0) info = 6;
-    if (delta <= EPSMCH * xnorm) info = 7;
-    if (gnorm <= EPSMCH) info = 8;
-  }
+  const int info = lm_step_info(actred, prered, ratio, delta, xnorm, gnorm, nfev, maxfev);
   if (lane == 0) {
     S.delta[f] = delta;
     S.par[f] = par;

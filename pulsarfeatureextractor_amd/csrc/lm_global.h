@@ -1,7 +1,8 @@
 // lm_global.h — MINPACK lmdif for one wavefront with the m rows in global memory.
 //
 // The same algorithm and arithmetic as lm_wave.h (fdjac2, qrfac with pivoting, Q^T f,
-// lmpar / qrsolv on the replicated n x n state, scipy's leastsq defaults), for problems whose
+// lmpar / qrsolv on the replicated n x n state, the step rule and info tests of its scalar
+// core, scipy's leastsq defaults), for problems whose
 // m rows do not fit in registers: the Freedman-Diaconis histograms of profiles with a tiny
 // interquartile range (thousands of bins, ProfileOperationsInterface.py:138-166).  Row
 // i = lane + 64 k of every m-vector lives at buf[k * 64 + lane] of its array, so each access
@@ -9,6 +10,8 @@
 // the slots in order, then by the wave butterfly (wsum), exactly as lm_wave.h does with
 // MPL = nsl slots.  The arrays of one solve (fvec, wa4, fjac[N]) take (N + 2) * 64 * nsl
 // doubles of per-wave scratch; the data stay L2-resident for the length of a solve.
+// Everything here ends in _mem (rows in memory); the arithmetic is the literal, uncontracted
+// MINPACK sequence over a run-time number of slots.
 #pragma once
 
 #include "lm_wave.h"
@@ -26,7 +29,7 @@ struct RowStore {
   static __host__ __device__ constexpr size_t doubles_per_slot() { return (size_t)(N + 2) * 64; }
 };
 
-__device__ __forceinline__ double enorm_g(const double* f, int nsl, int lane) {
+__device__ __forceinline__ double enorm_mem(const double* f, int nsl, int lane) {
   double p = 0.0;
   for (int k = 0; k < nsl; ++k) {
     const double v = f[k * 64 + lane];
@@ -36,7 +39,7 @@ __device__ __forceinline__ double enorm_g(const double* f, int nsl, int lane) {
 }
 
 template <int N>
-__device__ void qrfac_g(const RowStore<N>& rs, int (&ipvt)[N], double (&rdiag)[N], double (&acnorm)[N]) {
+__device__ void qrfac_mem(const RowStore<N>& rs, int (&ipvt)[N], double (&rdiag)[N], double (&acnorm)[N]) {
   const int lane = lane_id();
   const int nsl = rs.nsl;
   double wa[N];
@@ -137,8 +140,7 @@ __device__ void qrfac_g(const RowStore<N>& rs, int (&ipvt)[N], double (&rdiag)[N
 
 // fcn(p, f): f[k * 64 + lane] = residual of row lane + 64 k (0 for rows >= m)
 template <int N, class Fn>
-__device__ LMResult lmdif_g(const Fn& fcn, double (&x)[N], int maxfev, const RowStore<N>& rs) {
-  const double eps = 1.4901161193847656e-08;
+__device__ LMResult lmdif_mem(const Fn& fcn, double (&x)[N], int maxfev, const RowStore<N>& rs) {
   const int lane = lane_id();
   const int nsl = rs.nsl;
   double* fvec = rs.fvec();
@@ -149,15 +151,14 @@ __device__ LMResult lmdif_g(const Fn& fcn, double (&x)[N], int maxfev, const Row
   int info = 0;
   fcn(x, fvec);
   int nfev = 1;
-  double fnorm = enorm_g(fvec, nsl, lane);
+  double fnorm = enorm_mem(fvec, nsl, lane);
   double par = 0.0, xnorm = 0.0, delta = 0.0;
   int iter = 1;
   for (;;) {
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       const double temp = x[j];
-      double h = eps * fabs(temp);
-      if (h == 0.0) h = eps;
+      const double h = lm_fd_step(temp);
       x[j] = temp + h;
       fcn(x, wa4);
       x[j] = temp;
@@ -165,7 +166,7 @@ __device__ LMResult lmdif_g(const Fn& fcn, double (&x)[N], int maxfev, const Row
       for (int k = 0; k < nsl; ++k) fj[k * 64 + lane] = (wa4[k * 64 + lane] - fvec[k * 64 + lane]) / h;
     }
     nfev += N;
-    qrfac_g<N>(rs, ipvt, wa1, wa2);
+    qrfac_mem<N>(rs, ipvt, wa1, wa2);
     if (iter == 1) {
 #pragma unroll
       for (int j = 0; j < N; ++j) {
@@ -232,12 +233,7 @@ __device__ LMResult lmdif_g(const Fn& fcn, double (&x)[N], int maxfev, const Row
       if (iter == 1) delta = fmin(delta, pnorm);
       fcn(wa2, wa4);
       ++nfev;
-      const double fnorm1 = enorm_g(wa4, nsl, lane);
-      double actred = -1.0;
-      if (0.1 * fnorm1 < fnorm) {
-        const double q = fnorm1 / fnorm;
-        actred = 1.0 - q * q;
-      }
+      const double fnorm1 = enorm_mem(wa4, nsl, lane);
       double temp = 0.0;
 #pragma unroll
       for (int j = 0; j < N; ++j) wa3[j] = 0.0;
@@ -251,18 +247,8 @@ __device__ LMResult lmdif_g(const Fn& fcn, double (&x)[N], int maxfev, const Row
       const double temp2 = (sqrt(par) * pnorm) / fnorm;
       const double prered = temp1 * temp1 + (temp2 * temp2) / 0.5;
       const double dirder = -(temp1 * temp1 + temp2 * temp2);
-      ratio = 0.0;
-      if (prered != 0.0) ratio = actred / prered;
-      if (ratio <= 0.25) {
-        if (actred >= 0.0) temp = 0.5;
-        if (actred < 0.0) temp = 0.5 * dirder / (dirder + 0.5 * actred);
-        if (0.1 * fnorm1 >= fnorm || temp < 0.1) temp = 0.1;
-        delta = temp * fmin(delta, pnorm / 0.1);
-        par = par / temp;
-      } else if (par == 0.0 || ratio >= 0.75) {
-        delta = pnorm / 0.5;
-        par = 0.5 * par;
-      }
+      const LMStep st = lm_step_rule(fnorm1, fnorm, pnorm, prered, dirder, temp, delta, par);
+      ratio = st.ratio;
       if (ratio >= 1e-4) {
 #pragma unroll
         for (int j = 0; j < N; ++j) {
@@ -274,14 +260,9 @@ __device__ LMResult lmdif_g(const Fn& fcn, double (&x)[N], int maxfev, const Row
         fnorm = fnorm1;
         ++iter;
       }
-      if (fabs(actred) <= LM_FTOL && prered <= LM_FTOL && 0.5 * ratio <= 1.0) info = 1;
-      if (delta <= LM_XTOL * xnorm) info = 2;
-      if (fabs(actred) <= LM_FTOL && prered <= LM_FTOL && 0.5 * ratio <= 1.0 && info == 2) info = 3;
+      info = lm_converged(st.actred, prered, ratio, delta, xnorm);
       if (info != 0) break;
-      if (nfev >= maxfev) info = 5;
-      if (fabs(actred) <= EPSMCH && prered <= EPSMCH && 0.5 * ratio <= 1.0) info = 6;
-      if (delta <= EPSMCH * xnorm) info = 7;
-      if (gnorm <= EPSMCH) info = 8;
+      info = lm_terminated(st.actred, prered, ratio, delta, xnorm, gnorm, nfev, maxfev);
       if (info != 0) break;
     } while (ratio < 1e-4);
     if (info != 0) break;

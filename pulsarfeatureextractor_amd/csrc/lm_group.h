@@ -25,6 +25,8 @@
 // The arithmetic is MINPACK's (as lm_wave.h / lm_batch.h) with m-sums ordered per lane over
 // its rows and then as a butterfly over the 16 lanes: results differ from lm_batch.h only
 // in that summation order (last-bit), i.e. like any other non-sequential lmdif.
+// The forward-difference step, the step rule and info tests of a trial and the literal
+// build's in-place scaling are the shared ones (lm_wave.h's scalar core, blm_scaling).
 #pragma once
 
 #include <type_traits>
@@ -328,8 +330,6 @@ __device__ __forceinline__ void probe_keep(const double (&a)[M]) {
 template <int N, int MPL, int FPW, int G = GLM_G, class Fn>
 __device__ __forceinline__ void glm_outer(const Fn& fcn, int f, BlmState<N, FPW>& S, bool fresh,
                                           const double* hand) {
-  const double eps = 1.4901161193847656e-08;  // sqrt(max(epsfcn, epsmch)) = 2^-26
-  const int gl = glane<G>();
   double x[N], fvec[MPL];
   typename FnCache<Fn>::type cache;
 #pragma unroll
@@ -355,8 +355,7 @@ __device__ __forceinline__ void glm_outer(const Fn& fcn, int f, BlmState<N, FPW>
 #pragma unroll
   for (int j = 0; j < N; ++j) {
     const double temp = x[j];
-    double h = eps * fabs(temp);
-    if (h == 0.0) h = eps;
+    const double h = lm_fd_step(temp);
     x[j] = temp + h;
 #ifdef PFE_DUP_COLS
     {
@@ -372,6 +371,9 @@ __device__ __forceinline__ void glm_outer(const Fn& fcn, int f, BlmState<N, FPW>
     for (int k = 0; k < MPL; ++k) fjac[k][j] = la_quot(wa4[k] - fvec[k], h, rh);
   }
   nfev += N;
+  // the contracted build leaves acn squared and the scaling (diag, and xnorm / delta of a
+  // fresh fit) to the next SIMT phase, one fit per lane (blm_simt<.., true>)
+  constexpr bool SQ = !LA_EXACT_QUOTIENTS;
   int ipvt[N];
   double rdiag[N], acn[N], rajjv[N];
 #ifdef PFE_DUP_QR
@@ -388,29 +390,10 @@ __device__ __forceinline__ void glm_outer(const Fn& fcn, int f, BlmState<N, FPW>
   }
 #endif
   qrfac_g<N, MPL, G>(fjac, ipvt, rdiag, acn, rajjv);
-  // the contracted build leaves acn squared and the scaling (diag, and xnorm / delta of a
-  // fresh fit) to the next SIMT phase, one fit per lane (blm_simt<.., true>)
-  constexpr bool SQ = !LA_EXACT_QUOTIENTS;
-  double diag[N];
-  double xnorm = 0.0, delta = 0.0;
-  if (SQ) {
-  } else if (iter == 1) {
-    double wa3[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      diag[j] = acn[j];
-      if (acn[j] == 0.0) diag[j] = 1.0;
-    }
-#pragma unroll
-    for (int j = 0; j < N; ++j) wa3[j] = diag[j] * x[j];
-    xnorm = enorm_u(wa3);
-    delta = LM_FACTOR * xnorm;
-    if (delta == 0.0) delta = LM_FACTOR;
-  } else {
-#pragma unroll
-    for (int j = 0; j < N; ++j) diag[j] = S.diag[j][f];
-  }
-  double qtf[N];
+  double diag[N], qtf[N];
+  const int gl = glane<G>();
+  if constexpr (!SQ) blm_scaling(S, f, iter, gl, acn, x, diag);
+  // (Q^T) fvec -> qtf; restore the diagonal of R
 #pragma unroll
   for (int k = 0; k < MPL; ++k) wa4[k] = fvec[k];
   {
@@ -443,10 +426,6 @@ __device__ __forceinline__ void glm_outer(const Fn& fcn, int f, BlmState<N, FPW>
       S.qtf[j][f] = qtf[j];
       S.acn[j][f] = acn[j];
       S.ipvt[j][f] = ipvt[j];
-    }
-    if (!SQ && iter == 1) {
-      S.xnorm[f] = xnorm;
-      S.delta[f] = delta;
     }
     if (fresh) S.par[f] = 0.0;
     S.info[f] = -1;
@@ -482,24 +461,8 @@ __device__ __forceinline__ int glm_trial(const Fn& fcn, int f, BlmState<N, FPW>&
   const double pnorm = S.pnorm[f], prered = S.prered[f], dirder = S.dirder[f];
   const double gnorm = S.gnorm[f];
   int iter = S.iter[f];
-  double actred = -1.0;
-  if (0.1 * fnorm1 < fnorm) {
-    const double q = fnorm1 / fnorm;
-    actred = 1.0 - q * q;
-  }
-  double temp = S.tstale[f];
-  double ratio = 0.0;
-  if (prered != 0.0) ratio = actred / prered;
-  if (ratio <= 0.25) {
-    if (actred >= 0.0) temp = 0.5;
-    if (actred < 0.0) temp = 0.5 * dirder / (dirder + 0.5 * actred);
-    if (0.1 * fnorm1 >= fnorm || temp < 0.1) temp = 0.1;
-    delta = temp * fmin(delta, pnorm / 0.1);
-    par = par / temp;
-  } else if (par == 0.0 || ratio >= 0.75) {
-    delta = pnorm / 0.5;
-    par = 0.5 * par;
-  }
+  const LMStep st = lm_step_rule(fnorm1, fnorm, pnorm, prered, dirder, S.tstale[f], delta, par);
+  const double actred = st.actred, ratio = st.ratio;
   const bool accepted = ratio >= 1e-4;
   if (accepted) {
     double wa3[N];
@@ -509,16 +472,7 @@ __device__ __forceinline__ int glm_trial(const Fn& fcn, int f, BlmState<N, FPW>&
     fnorm = fnorm1;
     ++iter;
   }
-  int info = 0;
-  if (fabs(actred) <= LM_FTOL && prered <= LM_FTOL && 0.5 * ratio <= 1.0) info = 1;
-  if (delta <= LM_XTOL * xnorm) info = 2;
-  if (fabs(actred) <= LM_FTOL && prered <= LM_FTOL && 0.5 * ratio <= 1.0 && info == 2) info = 3;
-  if (info == 0) {
-    if (nfev >= maxfev) info = 5;
-    if (fabs(actred) <= EPSMCH && prered <= EPSMCH && 0.5 * ratio <= 1.0) info = 6;
-    if (delta <= EPSMCH * xnorm) info = 7;
-    if (gnorm <= EPSMCH) info = 8;
-  }
+  const int info = lm_step_info(actred, prered, ratio, delta, xnorm, gnorm, nfev, maxfev);
   if (hand && accepted && info == 0) HandOver<MPL, Fn, G>::put(hand, f, wa4, cache);
   if (gl == 0) {
     S.delta[f] = delta;

@@ -16,6 +16,12 @@
 //     and updated with identical arithmetic, so all control flow is wave-uniform.
 // Differences from a sequential MINPACK: sums over the m rows are formed in tree order
 // (last-bit differences), n-vector norms follow MINPACK's enorm exactly.
+//
+// This header also holds the scalar core that the other three forms of the solver call
+// (lm_global.h: rows in memory; lm_batch.h: a wave owns 32 fits; lm_group.h: pooled fits in
+// lane groups): the forward-difference step (lm_fd_step), the step rule (lm_step_rule) and the
+// info tests (lm_converged, lm_terminated, lm_step_info), called by all four, and the
+// first-iteration scaling of the two engines (lm_init_scaling).
 #pragma once
 
 #include "wave.h"
@@ -171,7 +177,7 @@ __device__ __forceinline__ double enorm_w(const double (&f)[MPL]) {
   return sqrt(wsum(p));
 }
 
-// row i = lane + 64*k is >= j (j < 64)
+// row i = lane + W*k is >= j (j < W)
 __device__ __forceinline__ bool row_ge(int lane, int k, int j) { return k > 0 || lane >= j; }
 
 // ---- qrfac (pivot = true) on the distributed m x N matrix a -------------------------------
@@ -644,7 +650,93 @@ __device__ __forceinline__ void lmpar(double (&r)[N][N], const int (&ipvt)[N],
   lmpar<N>(r, ipvt, diag, qtb, delta, par, x, sdiag, xp);
 }
 
-// ---- lmdif ----------------------------------------------------------------------------
+// ---- the scalar core of lmdif: one copy for every form of the solver ----------------------
+// fdjac2's forward-difference step for a parameter of value xj
+__device__ __forceinline__ double lm_fd_step(double xj) {
+  const double eps = 1.4901161193847656e-08;  // sqrt(max(epsfcn, epsmch)) = 2^-26
+  double h = eps * fabs(xj);
+  if (h == 0.0) h = eps;
+  return h;
+}
+
+// The scaling of the first iteration (mode 1): diag from the column norms of the first
+// Jacobian, xnorm = |diag x| and the initial step bound delta (the engines, through
+// blm_scaling)
+template <int N>
+__device__ __forceinline__ void lm_init_scaling(const double (&acnorm)[N], const double (&x)[N],
+                                                double (&diag)[N], double& xnorm, double& delta) {
+  double wa3[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    diag[j] = acnorm[j];
+    if (acnorm[j] == 0.0) diag[j] = 1.0;
+  }
+#pragma unroll
+  for (int j = 0; j < N; ++j) wa3[j] = diag[j] * x[j];
+  xnorm = enorm_u(wa3);
+  delta = LM_FACTOR * xnorm;
+  if (delta == 0.0) delta = LM_FACTOR;
+}
+
+// The step rule after a trial evaluation: the actual reduction, its ratio to the predicted
+// one, and the update of the step bound delta and of par.  temp: MINPACK's stale variable
+// (the last element of the permuted step) that the update reads when neither branch sets it.
+struct LMStep {
+  double actred, ratio;
+};
+__device__ __forceinline__ LMStep lm_step_rule(double fnorm1, double fnorm, double pnorm,
+                                               double prered, double dirder, double temp,
+                                               double& delta, double& par) {
+  double actred = -1.0;
+  if (0.1 * fnorm1 < fnorm) {
+    const double q = fnorm1 / fnorm;
+    actred = 1.0 - q * q;
+  }
+  double ratio = 0.0;
+  if (prered != 0.0) ratio = actred / prered;
+  if (ratio <= 0.25) {
+    if (actred >= 0.0) temp = 0.5;
+    if (actred < 0.0) temp = 0.5 * dirder / (dirder + 0.5 * actred);
+    if (0.1 * fnorm1 >= fnorm || temp < 0.1) temp = 0.1;
+    delta = temp * fmin(delta, pnorm / 0.1);
+    par = par / temp;
+  } else if (par == 0.0 || ratio >= 0.75) {
+    delta = pnorm / 0.5;
+    par = 0.5 * par;
+  }
+  return {actred, ratio};
+}
+
+// MINPACK's tests after the step rule, xnorm being that of the accepted point; 0: go on.
+// Convergence (info 1-3) and, only when those leave 0, termination (info 5-8): lmdif and
+// lmdif_mem break between the two halves, the engines' trial phases take lm_step_info.
+__device__ __forceinline__ int lm_converged(double actred, double prered, double ratio,
+                                            double delta, double xnorm) {
+  int info = 0;
+  if (fabs(actred) <= LM_FTOL && prered <= LM_FTOL && 0.5 * ratio <= 1.0) info = 1;
+  if (delta <= LM_XTOL * xnorm) info = 2;
+  if (fabs(actred) <= LM_FTOL && prered <= LM_FTOL && 0.5 * ratio <= 1.0 && info == 2) info = 3;
+  return info;
+}
+__device__ __forceinline__ int lm_terminated(double actred, double prered, double ratio,
+                                             double delta, double xnorm, double gnorm, int nfev,
+                                             int maxfev) {
+  int info = 0;
+  if (nfev >= maxfev) info = 5;
+  if (fabs(actred) <= EPSMCH && prered <= EPSMCH && 0.5 * ratio <= 1.0) info = 6;
+  if (delta <= EPSMCH * xnorm) info = 7;
+  if (gnorm <= EPSMCH) info = 8;
+  return info;
+}
+__device__ __forceinline__ int lm_step_info(double actred, double prered, double ratio,
+                                            double delta, double xnorm, double gnorm, int nfev,
+                                            int maxfev) {
+  int info = lm_converged(actred, prered, ratio, delta, xnorm);
+  if (info == 0) info = lm_terminated(actred, prered, ratio, delta, xnorm, gnorm, nfev, maxfev);
+  return info;
+}
+
+// ---- lmdif: one fit per wave ----------------------------------------------------------
 // fcn(p, f): fill f[k] with the residual of this lane's row i = lane + 64*k for i < m and
 // with 0 for i >= m.  Returns MINPACK's info (1-8); x holds the solution.
 struct LMResult {
@@ -654,7 +746,6 @@ struct LMResult {
 
 template <int N, int MPL, class Fn>
 __device__ __forceinline__ LMResult lmdif(const Fn& fcn, double (&x)[N], int maxfev) {
-  const double eps = 1.4901161193847656e-08;  // sqrt(max(epsfcn, epsmch)) = 2^-26
   double fvec[MPL], wa4[MPL];
   double fjac[MPL][N];
   double diag[N], qtf[N], wa1[N], wa2[N], wa3[N];
@@ -675,8 +766,7 @@ __device__ __forceinline__ LMResult lmdif(const Fn& fcn, double (&x)[N], int max
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       const double temp = x[j];
-      double h = eps * fabs(temp);
-      if (h == 0.0) h = eps;
+      const double h = lm_fd_step(temp);
       x[j] = temp + h;
       fcn(x, wa4);
       x[j] = temp;
@@ -767,11 +857,6 @@ __device__ __forceinline__ LMResult lmdif(const Fn& fcn, double (&x)[N], int max
       ++nfev;
       const double fnorm1 = enorm_w(wa4);
       LM_ADD(9, lm_clock() - t_tr);
-      double actred = -1.0;
-      if (0.1 * fnorm1 < fnorm) {
-        const double q = fnorm1 / fnorm;
-        actred = 1.0 - q * q;
-      }
       double temp = 0.0;
 #pragma unroll
       for (int j = 0; j < N; ++j) wa3[j] = 0.0;
@@ -785,18 +870,8 @@ __device__ __forceinline__ LMResult lmdif(const Fn& fcn, double (&x)[N], int max
       const double temp2 = (sqrt(par) * pnorm) / fnorm;
       const double prered = temp1 * temp1 + (temp2 * temp2) / 0.5;
       const double dirder = -(temp1 * temp1 + temp2 * temp2);
-      ratio = 0.0;
-      if (prered != 0.0) ratio = actred / prered;
-      if (ratio <= 0.25) {
-        if (actred >= 0.0) temp = 0.5;
-        if (actred < 0.0) temp = 0.5 * dirder / (dirder + 0.5 * actred);
-        if (0.1 * fnorm1 >= fnorm || temp < 0.1) temp = 0.1;
-        delta = temp * fmin(delta, pnorm / 0.1);
-        par = par / temp;
-      } else if (par == 0.0 || ratio >= 0.75) {
-        delta = pnorm / 0.5;
-        par = 0.5 * par;
-      }
+      const LMStep st = lm_step_rule(fnorm1, fnorm, pnorm, prered, dirder, temp, delta, par);
+      ratio = st.ratio;
       if (ratio >= 1e-4) {
 #pragma unroll
         for (int j = 0; j < N; ++j) {
@@ -809,14 +884,9 @@ __device__ __forceinline__ LMResult lmdif(const Fn& fcn, double (&x)[N], int max
         fnorm = fnorm1;
         ++iter;
       }
-      if (fabs(actred) <= LM_FTOL && prered <= LM_FTOL && 0.5 * ratio <= 1.0) info = 1;
-      if (delta <= LM_XTOL * xnorm) info = 2;
-      if (fabs(actred) <= LM_FTOL && prered <= LM_FTOL && 0.5 * ratio <= 1.0 && info == 2) info = 3;
+      info = lm_converged(st.actred, prered, ratio, delta, xnorm);
       if (info != 0) break;
-      if (nfev >= maxfev) info = 5;
-      if (fabs(actred) <= EPSMCH && prered <= EPSMCH && 0.5 * ratio <= 1.0) info = 6;
-      if (delta <= EPSMCH * xnorm) info = 7;
-      if (gnorm <= EPSMCH) info = 8;
+      info = lm_terminated(st.actred, prered, ratio, delta, xnorm, gnorm, nfev, maxfev);
       if (info != 0) break;
     } while (ratio < 1e-4);
     if (info != 0) break;

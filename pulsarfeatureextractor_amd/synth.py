@@ -77,6 +77,26 @@ def bates_batch(n: int, lp: int = 128, nsub: int = 16, lsb: int = 128, ndm: int 
     return {"prof": prof, "sub": sub, "dmcurve": dmc, "scal": scal}
 
 
+def wide_histogram_batch(n, seed):
+    """Profiles with low noise under a strong narrow pulse: Freedman-Diaconis bin counts of
+    ~40 (pooled kernels), ~100-190 (deferred to the wave kernel, > 64 bins), ~350-390
+    (the 1024-bin wave kernel, > 256 bins) and, from quantised sigma ~ 0.5 noise, often
+    1000-1600 (k_ghist_wide, rows in global scratch)."""
+    b = bates_batch(n, seed=seed)
+    rng = np.random.default_rng(seed)
+    lp = b["prof"].shape[1]
+    x = np.arange(lp)
+    prof = np.empty((n, lp))
+    for i in range(n):
+        kind = i % 4
+        sd = (2.5, 0.7, 6.0, 0.5)[kind]
+        base = rng.normal(100 if kind != 1 else 50, sd, lp)
+        mu, w = rng.uniform(10, lp - 10), rng.uniform(1.0, 3.0)
+        prof[i] = base + 150 * np.exp(-0.5 * ((x - mu) / w) ** 2)
+    b["prof"] = np.clip(np.rint(prof), 0, 255).astype(np.uint8)
+    return b
+
+
 def lyon_batch_torch(n: int, lp: int = 128, ld: int = 128, seed: int = BASE_SEED + 2,
                      device="cuda"):
     """Same recipe generated on the GPU with torch (bench-sized batches)."""

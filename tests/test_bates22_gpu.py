@@ -37,7 +37,7 @@ import pytest
 
 from golden_util import (FIT_GROUPS, GOLDEN, SELF_NOISY, bates_inputs, envelope_check, load,
                          oracle_with_floor)
-from pulsarfeatureextractor_amd.synth import bates_batch
+from pulsarfeatureextractor_amd.synth import bates_batch, wide_histogram_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -277,26 +277,6 @@ def test_pooled_group_solver(engine, lp, n):
     o2, s2 = engine.bates22(b["prof"][perm], b["sub"][perm], b["dmcurve"][perm], b["scal"][perm])
     assert np.array_equal(s2, s1[perm])
     assert np.array_equal(np.nan_to_num(o2, nan=7.0), np.nan_to_num(o1[perm], nan=7.0))
-
-
-def wide_histogram_batch(n, seed):
-    """Profiles with low noise under a strong narrow pulse: Freedman-Diaconis bin counts of
-    ~40 (pooled kernels), ~100-190 (deferred to the wave kernel, > 64 bins), ~350-390
-    (the 1024-bin wave kernel, > 256 bins) and, from quantised sigma ~ 0.5 noise, often
-    1000-1600 (k_ghist_wide, rows in global scratch)."""
-    b = bates_batch(n, seed=seed)
-    rng = np.random.default_rng(seed)
-    lp = b["prof"].shape[1]
-    x = np.arange(lp)
-    prof = np.empty((n, lp))
-    for i in range(n):
-        kind = i % 4
-        sd = (2.5, 0.7, 6.0, 0.5)[kind]
-        base = rng.normal(100 if kind != 1 else 50, sd, lp)
-        mu, w = rng.uniform(10, lp - 10), rng.uniform(1.0, 3.0)
-        prof[i] = base + 150 * np.exp(-0.5 * ((x - mu) / w) ** 2)
-    b["prof"] = np.clip(np.rint(prof), 0, 255).astype(np.uint8)
-    return b
 
 
 def test_wide_histograms_vs_oracle(engine):

@@ -7,7 +7,10 @@ kernel changes that must not move any result (e.g. a cheaper but exact division)
   python tools/lib_outputs.py compare out_a.npz out_b.npz
 
 Inputs: the golden PHCX sets and synthetic batches (pulsarfeatureextractor_amd.synth) of
-64- and 128-bin candidates, the default (pooled) solver and the batched one.
+64- and 128-bin candidates, the default (pooled) solver and the batched one; 256- and 200-bin
+batches (32-lane groups, ragged rows) with both; a 512-bin batch (the batched default, 16 rows
+per lane); a 128-bin batch with the wave-per-fit solver; and synth.wide_histogram_batch
+(lmdif through k_ghist, the memory-rows solver through k_ghist_wide).
 """
 import os
 import sys
@@ -22,7 +25,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 def dump(path):
     from golden_util import bates_inputs, load
     from pulsarfeatureextractor_amd._native import Engine
-    from pulsarfeatureextractor_amd.synth import bates_batch
+    from pulsarfeatureextractor_amd.synth import bates_batch, wide_histogram_batch
 
     res = {}
     with Engine(0) as e:
@@ -62,12 +65,28 @@ def dump(path):
             out, st = e.pfd_bates22(profs, subfreqs, pscal)
             res[f"{tag}_b22_out"] = np.asarray(out)
             res[f"{tag}_b22_st"] = np.asarray(st)
+        def batch(n, lp, seed):
+            b = bates_batch(n, lp=lp, lsb=lp, seed=seed)
+            return (b["prof"], b["sub"], b["dmcurve"], b["scal"])
+
+        sets["synth256"] = batch(4000, 256, 85)
+        sets["synth200"] = batch(2000, 200, 86)
         for solver in ("pooled", "batched"):
             e.set_option("solver", solver)
             for name, args in sets.items():
                 out, st = e.bates22(*args)
                 res[f"{name}_{solver}_out"] = np.asarray(out)
                 res[f"{name}_{solver}_st"] = np.asarray(st)
+        # one set per remaining path: the wave-per-fit solver, the batched default above 256
+        # bins, and histograms wide enough for k_ghist and k_ghist_wide
+        b = wide_histogram_batch(80, 5)
+        for name, solver, args in (("synth128w", "wave", batch(2000, 128, 87)),
+                                   ("synth512", "pooled", batch(200, 512, 88)),
+                                   ("widehist", "pooled", (b["prof"], b["sub"], b["dmcurve"], b["scal"]))):
+            e.set_option("solver", solver)
+            out, st = e.bates22(*args)
+            res[f"{name}_{solver}_out"] = np.asarray(out)
+            res[f"{name}_{solver}_st"] = np.asarray(st)
     np.savez(path, **res)
     print("dumped", path, len(res))
 

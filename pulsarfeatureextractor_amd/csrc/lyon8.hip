@@ -19,9 +19,10 @@
 //     skew/kurt to a few ulp.
 //   * Fast path (lp == ld == L in {64,128,256}, 16-B aligned rows): L/32 lanes per
 //     candidate, each lane streams 32 B of the profile row and 32 B of the DM row with
-//     dwordx4 loads; the group reduces with DPP quad/half-row butterflies; each lane then
-//     finalises 8/(L/32) of the candidate's 8 outputs and stores them as one contiguous
-//     16/32/8-byte vector, so a wave writes a dense 1 KiB span of the output matrix.
+//     dwordx4 loads; the group reduces with DPP quad/half-row butterflies; the rows of the
+//     U groups of a wave step are then shared out, one (group, row) per lane where there
+//     are enough of them, finalised once (32-bit / fp64 / two 32 x 32 -> 64 products: stats4)
+//     and stored so that a store instruction of the wave writes dense spans of the output.
 //   * Generic path (any lengths/alignment): one wave per (candidate,row), byte loads,
 //     64-bit per-lane sums, 128-bit finalisation.
 
@@ -149,23 +150,41 @@ __device__ __forceinline__ void acc2_reduce(Acc2& a) {
   a.t4 = group_sum_u64<G>(a.t4);
 }
 
-// the four statistics of one row from its exact sums; n = L (a power of two)
+// the four statistics of one row from its exact sums; n = L (a power of two, L = 2^K).
+// The numerators are the exact integers of moments_i64, evaluated in the narrowest exact form
+// the bounds of a byte row of L <= 256 allow (y in [-128, 127]):
+//   |T1| <= 2^15, 0 <= T2 <= 2^22, |T3| <= 2^29, 0 <= T4 <= 2^36, T1^2 <= 2^30
+//   * N2 = L T2 - T1^2 in [0, 2^30]: 32-bit, T1^2 by the 24-bit multiply;
+//   * N3: every product and partial sum is an integer below 2^48, so plain fp64 multiplies
+//     and adds are exact (no rounding anywhere, fused or not) and the sum is the double
+//     the 64-bit integer would convert to;
+//   * N4 in [0, 2^61) (m4 <= 255^4 / 12): modulo 2^64 from two 32 x 32 -> 64 products
+//     (T1 T3 and T1^2 W, below) and shifts by powers of L.
 template <int L>
 __device__ __forceinline__ void stats4(const Acc2& a, double (&st)[4]) {
+  static_assert(L <= 256 && (L & (L - 1)) == 0, "bounds of the narrow numerators");
+  constexpr int K = L == 256 ? 8 : L == 128 ? 7 : L == 64 ? 6 : L == 32 ? 5 : -1;
+  static_assert(K > 0 && (1 << K) == L, "L = 2^K");
   constexpr double IN1 = 1.0 / L, IN2 = IN1 * IN1, IN3 = IN2 * IN1, IN4 = IN2 * IN2;
-  const long long S1 = (long long)a.s1;
-  const long long T1 = S1 - 128ll * L;                                    // sum y
-  const long long T2 = (long long)a.s2 - 256ll * S1 + 16384ll * L;         // sum y^2
-  const long long T3 = a.t3;
   typedef unsigned long long u64;
-  const long long N2 = (long long)L * T2 - T1 * T1;
-  const long long T1s = T1 * T1;
-  const long long N3 = (long long)L * L * T3 - 3ll * L * T1 * T2 + 2ll * T1s * T1;
-  const u64 N4 = (u64)L * L * L * a.t4 - 4ull * (u64)L * L * (u64)(T1 * T3) +
-                 6ull * (u64)L * (u64)(T1s * T2) - 3ull * (u64)T1s * (u64)T1s;
-  const double mean = (double)S1 * IN1;
+  const int T1 = (int)a.s1 - 128 * L;                                     // sum y
+  const int T2 = (int)(a.s2 - 256u * a.s1) + 16384 * L;                   // sum y^2
+  const int T3 = a.t3;
+  const int T1s = __mul24(T1, T1);
+  const int N2 = L * T2 - T1s;
+  const double d1 = (double)T1, d1s = (double)T1s;
+  const double N3 = ((double)T3 * (double)(L * L) - (d1 * (double)T2) * (double)(3 * L)) +
+                    (d1s * d1) * 2.0;
+  // 6 L T1^2 T2 - 3 T1^4 = 3 T1^2 W with W = 2 L T2 - T1^2 = L T2 + N2 in [0, 2^31): the
+  // products are kept opaque so that the shifts are not folded back into 64-bit multiplies
+  const uint32_t W = (uint32_t)(2 * L) * (uint32_t)T2 - (uint32_t)T1s;
+  u64 p13 = (u64)((long long)T1 * (long long)T3);
+  u64 pw = (u64)(uint32_t)T1s * (u64)W;
+  asm("" : "+v"(p13), "+v"(pw));
+  const u64 N4 = (a.t4 << (3 * K)) - (p13 << (2 * K + 2)) + ((pw << 1) + pw);
+  const double mean = (double)a.s1 * IN1;
   const double m2 = (double)N2 * IN2;
-  const double m3 = (double)N3 * IN3;
+  const double m3 = N3 * IN3;
   const double m4 = (double)N4 * IN4;
   const double sd = sqrt(m2);
   const double e = 2.220446049250313e-16 * mean;
@@ -182,6 +201,13 @@ __device__ __forceinline__ void stats4(const Acc2& a, double (&st)[4]) {
 // L = 128, U = 4: measured +5% HBM throughput over one group, tools/membw.hip), and all
 // 4*U dwordx4 loads are issued unconditionally (out-of-range groups re-read the last row)
 // before any is consumed, so the compiler's vmcnt counting keeps them all in flight.
+// The U groups are accumulated and reduced first; the 2 U rows of a candidate slot are then
+// finalised (stats4: sqrt, two divisions, the exact numerators) by as few lanes as there are
+// rows -- one lane per row at (128, U >= 2) and (256, 4), two at (256, 2) -- instead of by
+// the LPC / 2 lanes that streamed the row.
+constexpr int DPP_QUAD_0011 = 0x50;  // quad_perm [0,0,1,1]
+constexpr int DPP_QUAD_2233 = 0xFA;  // quad_perm [2,2,3,3]
+
 template <int L, int U>
 __global__ __launch_bounds__(256) void lyon8_u8_fast3(const uint8_t* __restrict__ prof,
                                                       int64_t ps,
@@ -190,57 +216,120 @@ __global__ __launch_bounds__(256) void lyon8_u8_fast3(const uint8_t* __restrict_
                                                       double* __restrict__ out) {
   constexpr int LPC = L / 32;
   constexpr int CPW = 64 / LPC;
-  constexpr int SPL = 8 / LPC;
+  constexpr int STEP = CPW * U;               // candidates of a wave step
+  constexpr int HL = LPC / 2;                 // lanes of a candidate per row (profile / DM)
+  constexpr int GPR = HL < U ? HL : U;        // groups finalised in one round
+  constexpr int ROUNDS = U / GPR;
+  constexpr int DUP = HL / GPR;               // lanes that finalise the same row
+  constexpr int SPL = 4 / DUP;                // statistics each of them stores
   const int lane = threadIdx.x & 63;
   const int sub = lane % LPC;
   const int cw = lane / LPC;
-  const int j0 = sub * SPL;
-  const bool is_dm = j0 >= 4;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t step = (int64_t)CPW * U;
-  const int64_t stride = (((int64_t)gridDim.x * blockDim.x) >> 6) * step;
-  for (int64_t base = wave * step; base < n; base += stride) {
+  const int row = sub & 1;                    // 0 profile, 1 DM
+  const int g = (sub >> 1) % GPR;             // group of the round
+  const int part = (sub >> 1) / GPR;          // which SPL of the row's 4 statistics
+  // the wave's rows are wave-uniform: base and the row pointers live in SGPRs, lanes add
+  // 32-bit offsets (the host sends strides with STEP * stride >= 2^31 down the generic path)
+  const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int wpb = (int)(blockDim.x >> 6);
+  const int64_t wave = (int64_t)blockIdx.x * wpb + wib;
+  const int64_t stride = (int64_t)gridDim.x * wpb * STEP;
+  const uint32_t ps32 = (uint32_t)ps, ds32 = (uint32_t)ds;
+  uint32_t prow[U], drow[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    prow[u] = (uint32_t)(u * CPW + cw) * ps32;
+    drow[u] = (uint32_t)(u * CPW + cw) * ds32;
+  }
+  const uint32_t lsub = (uint32_t)sub * 32u;
+  const uint32_t oofs = (uint32_t)((g * CPW + cw) * 64 + row * 32 + part * (SPL * 8));
+  for (int64_t base = wave * STEP; base < n; base += stride) {
+    const int64_t rem = n - base;
+    const int last = rem < STEP ? (int)rem - 1 : STEP - 1;  // last candidate of the step in range
+    const uint8_t* pb = prof + base * ps;
+    const uint8_t* db = dm + base * ds;
+    const uint32_t pmax = (uint32_t)last * ps32, dmax = (uint32_t)last * ds32;
     u32x4 p[U][2], d[U][2];
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      int64_t c = base + u * CPW + cw;
-      c = c < n ? c : n - 1;
-      const u32x4* pp = reinterpret_cast<const u32x4*>(prof + c * ps + sub * 32);
-      const u32x4* dp = reinterpret_cast<const u32x4*>(dm + c * ds + sub * 32);
+    for (int u = 0; u < U; ++u) {  // out-of-range candidates re-read the last row
+      const uint32_t po = (prow[u] < pmax ? prow[u] : pmax) + lsub;
+      const uint32_t dq = (drow[u] < dmax ? drow[u] : dmax) + lsub;
+      const u32x4* pp = reinterpret_cast<const u32x4*>(pb + po);
+      const u32x4* dp = reinterpret_cast<const u32x4*>(db + dq);
       p[u][0] = __builtin_nontemporal_load(pp);
       p[u][1] = __builtin_nontemporal_load(pp + 1);
       d[u][0] = __builtin_nontemporal_load(dp);
       d[u][1] = __builtin_nontemporal_load(dp + 1);
     }
+    // the reduced sums of all U groups (every lane of a candidate holds its own)
+    Acc2 sp[U], sd[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int64_t c = base + u * CPW + cw;
-      Acc2 sp = {0, 0, 0, 0}, sd = {0, 0, 0, 0};
-      acc2_x4(p[u][0], sp);
-      acc2_x4(p[u][1], sp);
-      acc2_x4(d[u][0], sd);
-      acc2_x4(d[u][1], sd);
-      acc2_reduce<LPC>(sp);
-      acc2_reduce<LPC>(sd);
+      sp[u] = {0, 0, 0, 0};
+      sd[u] = {0, 0, 0, 0};
+      acc2_x4(p[u][0], sp[u]);
+      acc2_x4(p[u][1], sp[u]);
+      acc2_x4(d[u][0], sd[u]);
+      acc2_x4(d[u][1], sd[u]);
+      acc2_reduce<LPC>(sp[u]);
+      acc2_reduce<LPC>(sd[u]);
+    }
+    // finalise: lane `sub` of a candidate takes row sub & 1 of group u0 + g, so a row is
+    // finalised by DUP = max(1, LPC / (2 U)) lanes, not LPC / 2
+    double* ob = out + base * 8;
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+      const int u0 = r * GPR;
       Acc2 s;
-      s.s1 = is_dm ? sd.s1 : sp.s1;
-      s.s2 = is_dm ? sd.s2 : sp.s2;
-      s.t3 = is_dm ? sd.t3 : sp.t3;
-      s.t4 = is_dm ? sd.t4 : sp.t4;
+      s.s1 = row ? sd[u0].s1 : sp[u0].s1;
+      s.s2 = row ? sd[u0].s2 : sp[u0].s2;
+      s.t3 = row ? sd[u0].t3 : sp[u0].t3;
+      s.t4 = row ? sd[u0].t4 : sp[u0].t4;
+#pragma unroll
+      for (int k = 1; k < GPR; ++k) {
+        const bool mine = g == k;
+        const Acc2& a = sp[u0 + k];
+        const Acc2& b = sd[u0 + k];
+        s.s1 = mine ? (row ? b.s1 : a.s1) : s.s1;
+        s.s2 = mine ? (row ? b.s2 : a.s2) : s.s2;
+        s.t3 = mine ? (row ? b.t3 : a.t3) : s.t3;
+        s.t4 = mine ? (row ? b.t4 : a.t4) : s.t4;
+      }
       double st[4];
       stats4<L>(s, st);
-      if (c < n) {
-        double* o = out + c * 8 + j0;
+      if constexpr (SPL == 4 && LPC == 4) {
+        // L = 128: a quad holds the rows (g0 P, g0 DM, g1 P, g1 DM), 32 B each.  Stored from
+        // there, each 16-B store instruction would cover alternate 16-B pieces of two 1 KiB
+        // spans (measured: WRITE_SIZE 677 MB per 10M-row launch instead of 640, and 5 % more
+        // time).  A quad exchange first: store j writes the 64 B of group u0 + j's candidate,
+        // lane `sub` its 16-B piece `sub`, so every store instruction is a dense 1 KiB.
+        // (every lane runs all eight moves: a DPP move inside a branch reads disabled lanes)
+        const bool hi = sub & 1;
+        double a[4], b[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          a[k] = dpp_f64<DPP_QUAD_0011>(st[k]);
+          b[k] = dpp_f64<DPP_QUAD_2233>(st[k]);
+        }
+        const f64x2 v0 = {hi ? a[2] : a[0], hi ? a[3] : a[1]};
+        const f64x2 v1 = {hi ? b[2] : b[0], hi ? b[3] : b[1]};
+        char* o = reinterpret_cast<char*>(ob) + (uint32_t)(u0 * CPW * 64) +
+                  (uint32_t)(cw * 64 + sub * 16);
+        if (u0 * CPW + cw <= last) __builtin_nontemporal_store(v0, reinterpret_cast<f64x2*>(o));
+        if (u0 * CPW + CPW + cw <= last)
+          __builtin_nontemporal_store(v1, reinterpret_cast<f64x2*>(o + CPW * 64));
+      } else
+      if (u0 * CPW + g * CPW + cw <= last) {
+        double* o = reinterpret_cast<double*>(reinterpret_cast<char*>(ob) +
+                                              (uint32_t)(u0 * CPW * 64) + oofs);
         if constexpr (SPL == 4) {
           __builtin_nontemporal_store((f64x2){st[0], st[1]}, reinterpret_cast<f64x2*>(o));
           __builtin_nontemporal_store((f64x2){st[2], st[3]}, reinterpret_cast<f64x2*>(o) + 1);
         } else if constexpr (SPL == 2) {
-          const bool hi2 = (j0 & 3) != 0;
-          __builtin_nontemporal_store((f64x2){hi2 ? st[2] : st[0], hi2 ? st[3] : st[1]},
+          __builtin_nontemporal_store((f64x2){part ? st[2] : st[0], part ? st[3] : st[1]},
                                       reinterpret_cast<f64x2*>(o));
         } else {
-          const int k = j0 & 3;
-          const double v = k == 0 ? st[0] : k == 1 ? st[1] : k == 2 ? st[2] : st[3];
+          const double v = part == 0 ? st[0] : part == 1 ? st[1] : part == 2 ? st[2] : st[3];
           __builtin_nontemporal_store(v, o);
         }
       }
@@ -1345,7 +1434,7 @@ namespace pfe {
 
 static inline int grid_for(int64_t work_waves, int cap) {
   // 4 waves per block; capped (handle option PFE_OPT_LYON8_BLOCKS, default 256 CUs x 64
-  // blocks: 7 resident waves per SIMD at 71 VGPRs; 32 blocks per CU were +1-2 % over 8
+  // blocks: 8 resident waves per SIMD at 64 VGPRs; 32 blocks per CU were +1-2 % over 8
   // (tools/ab_lyon8_grid.sh), 64 a further 1.3 % over 32 (profiles/r03_ab_lyon8_grid.txt))
   // and grid-stride the rest
   int64_t blocks = (work_waves + 3) / 4;
@@ -1532,7 +1621,9 @@ hipError_t launch_lyon8_u8(const uint8_t* prof, int64_t ps, int lp, const uint8_
     }
     return hipGetLastError();
   }
-  if (aligned && lp == ld && (lp == 64 || lp == 128 || lp == 256)) {
+  // lyon8_u8_fast3 adds 32-bit lane offsets (up to 128 rows) to a wave's base row
+  const bool near = ps >= 0 && ds >= 0 && ps < (1 << 24) && ds < (1 << 24);
+  if (aligned && near && lp == ld && (lp == 64 || lp == 128 || lp == 256)) {
     const int U = o.lyon8_burst;  // 1, 2 (default) or 4 candidate groups per wave step
     const int cpw = 64 / (lp / 32) * U;
     const int grid = grid_for((n + cpw - 1) / cpw, o.lyon8_blocks);

@@ -10,7 +10,8 @@ Inputs: the golden PHCX sets and synthetic batches (pulsarfeatureextractor_amd.s
 64- and 128-bin candidates, the default (pooled) solver and the batched one; 256- and 200-bin
 batches (32-lane groups, ragged rows) with both; a 512-bin batch (the batched default, 16 rows
 per lane); a 128-bin batch with the wave-per-fit solver; and synth.wide_histogram_batch
-(lmdif through k_ghist, the memory-rows solver through k_ghist_wide).
+(lmdif through k_ghist, the memory-rows solver through k_ghist_wide).  The 8 Lyon features of
+pfe_lyon8_u8 are dumped too: 64 / 128 / 256-byte rows at every burst, two DataBlock lengths.
 """
 import os
 import sys
@@ -65,6 +66,19 @@ def dump(path):
             out, st = e.pfd_bates22(profs, subfreqs, pscal)
             res[f"{tag}_b22_out"] = np.asarray(out)
             res[f"{tag}_b22_st"] = np.asarray(st)
+        # pfe_lyon8_u8: the stream kernel at every row length and burst (an odd row count, so
+        # the last wave step is partial), and two DataBlock lengths
+        from pulsarfeatureextractor_amd.synth import lyon_batch
+
+        for L in (64, 128, 256):
+            prof, dm = lyon_batch(20003, L, L, seed=9200 + L, adversarial=True)
+            for burst in (1, 2, 4):
+                with e.options(lyon8_burst=burst):
+                    res[f"lyon8_{L}_u{burst}_out"] = np.asarray(e.lyon8(prof, dm))
+        for ld in (15360, 16384):
+            prof, dm = lyon_batch(3001, 128, ld, seed=9300 + ld, adversarial=True)
+            res[f"lyon8_128x{ld}_out"] = np.asarray(e.lyon8(prof, dm))
+
         def batch(n, lp, seed):
             b = bates_batch(n, lp=lp, lsb=lp, seed=seed)
             return (b["prof"], b["sub"], b["dmcurve"], b["scal"])

@@ -132,6 +132,9 @@ int pfe_synchronize(pfe_handle* h);
  *                        their quad), and one-chunk rows of 17-32 leaves are taken two per
  *                        wave; 2: the chain splits only; 0: one lane per leaf.  Mean and std
  *                        the same bits with every value, skew / kurt within 1e-12
+ *   PFE_OPT_PFD_GLOBAL   PFD preprocessing: 0 (default) = folds whose sub-band profiles fit the
+ *                        LDS stay on chip and every other shape goes through global scratch of
+ *                        the handle; 1 = every shape through global scratch (same bits)
  * Returns PFE_EINVAL for an unknown option or an out-of-range value.
  * --------------------------------------------------------------------------------------- */
 #define PFE_OPT_SOLVER 1
@@ -144,6 +147,7 @@ int pfe_synchronize(pfe_handle* h);
 #define PFE_OPT_LYON8_DM 8
 #define PFE_OPT_PFD_SPLIT 9
 #define PFE_OPT_LYON8_DM_SPLIT 10
+#define PFE_OPT_PFD_GLOBAL 11
 #define PFE_SOLVER_POOLED 0
 #define PFE_SOLVER_BATCHED 1
 #define PFE_SOLVER_WAVE 2
@@ -265,7 +269,12 @@ int pfe_dmfit4(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* sta
  * Outputs (each may be NULL): profile[n][proflen] (0..255 fp64, also the --profile bins of
  * PFDFile.computeProfileScores :479-492), chis[n][PFE_PFD_NDM] (the float32 DM curve),
  * lyon8[n][8] = [profile mean, std, skew, kurt, DM-curve mean, std, skew, kurt].
- * status[i] = PFE_ST_PFD_DMCURVE_FAIL when numdms == 1 (the reference raises on dms[0]). */
+ * status[i] = PFE_ST_PFD_DMCURVE_FAIL when numdms == 1 (the reference raises on dms[0]).
+ * Any npart >= 1, nsub >= 1 and proflen >= 2 with 6 * proflen + 3.5 * nsub doubles of per-fold
+ * vectors within the 160 KiB of LDS (so every nsub <= 1024 with proflen <= 2048): a fold
+ * whose nsub x proflen sub-band profiles fit the LDS as well (about nsub * proflen <= 20000)
+ * is kept on chip, every other shape in global scratch of the handle (up to 1 GiB).  Beyond
+ * that, and for proflen > 65535, PFE_EINVAL. */
 #define PFE_PFD_NSCAL 8
 #define PFE_PFD_BESTDM 0
 #define PFE_PFD_BINSPERSEC 1
@@ -295,7 +304,8 @@ int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* 
  * getDMFittings (s16-s19, the clamped 4-parameter fit to the chi^2-vs-DM curve, :274-393) and
  * getSubbandParameters over the dedispersed sub-band profiles (s20-s22, :401-466).
  * Same inputs as pfe_pfd_dmprof (scal[PFE_PFD_BARY_P1] is used); out[n][22]; status bits as
- * pfe_bates22 (PFE_ST_DMFIT_FAIL when numdms == 1).  LDS-resident limit as pfe_pfd_dmprof. */
+ * pfe_bates22 (PFE_ST_DMFIT_FAIL when numdms == 1).  nsub >= 2 and 8 <= proflen <= 1024 (the
+ * fits); within those, the shapes of pfe_pfd_dmprof (so every nsub <= 1024). */
 int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
                     uint32_t flags);
 

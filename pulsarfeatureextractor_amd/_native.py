@@ -80,6 +80,7 @@ OPTIONS = {
     "lyon8_dm": 8,      # DataBlock kernels: 0 default, 1 round 3, 2 exact power sums (pfe.h)
     "pfd_split": 9,     # 0 fused kernel (default), 1 part sums streamed beside the sweep
     "lyon8_dm_split": 10,  # 1 (default) chain splits + paired one-chunk rows, 2 splits only, 0 off
+    "pfd_global": 11,   # 0 folds that fit stay in LDS (default), 1 every fold through global scratch
 }
 SOLVERS = {"pooled": 0, "batched": 1, "wave": 2}
 

@@ -18,7 +18,7 @@ BUILDDIR = os.path.join(HERE, "lib", "obj")
 LIB = os.path.join(LIBDIR, "libpfe.so")
 SOURCES = ["capi.hip", "lyon8.hip", "bates22.hip", "bates_sine_dm_sub.hip", "bates_gauss.hip", "bates_gauss_peel.hip",
            "bates_gauss_dg8.hip", "subband.hip",
-           "pfd.hip", "pfd22.hip"]
+           "pfd.hip", "pfd22.hip", "pfd_global.hip"]
 # The Levenberg-Marquardt translation units are compiled without the two-address v_fmac_f64:
 # with it the register allocator copies the accumulator (a v_mov_b64 per fma whose addend
 # stays live -- every polynomial coefficient of exp, every Householder update), ~600 extra
@@ -83,6 +83,8 @@ def build(verbose: bool = False, force: bool = False, variant: str = "",
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
+        if csrc and not os.path.exists(s):
+            continue  # a variant from an earlier revision that has no such translation unit
         o = os.path.join(builddir, src.replace(".hip", ".o"))
         objs.append(o)
         if force or _needs(o, [s] + headers):

@@ -289,6 +289,10 @@ int pfe_set_option(pfe_handle* h, int32_t option, int64_t v) {
       if (v < 0 || v > 2) break;
       o.lyon8_dm_split = (int)v;
       return PFE_OK;
+    case PFE_OPT_PFD_GLOBAL:
+      if (v != 0 && v != 1) break;
+      o.pfd_global = (int)v;
+      return PFE_OK;
     default:
       return set_err(h, PFE_EINVAL, "pfe_set_option: unknown option %d", option);
   }
@@ -310,6 +314,7 @@ int pfe_get_option(const pfe_handle* h, int32_t option, int64_t* v) {
     case PFE_OPT_LYON8_DM: *v = o.lyon8_dm; return PFE_OK;
     case PFE_OPT_PFD_SPLIT: *v = o.pfd_split; return PFE_OK;
     case PFE_OPT_LYON8_DM_SPLIT: *v = o.lyon8_dm_split; return PFE_OK;
+    case PFE_OPT_PFD_GLOBAL: *v = o.pfd_global; return PFE_OK;
     default: return PFE_EINVAL;
   }
 }
@@ -785,6 +790,18 @@ int pfe_params4(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* st
 }
 
 // ---- PFD -------------------------------------------------------------------------------
+// folds that fit the LDS keep the LDS-resident kernels; every other shape (and every shape
+// under PFE_OPT_PFD_GLOBAL = 1) takes k_pfd_dmprof_g on slabs of the handle's scratch
+static bool pfd_use_global(const pfe_handle* h, const pfe_pfd_in* in) {
+  return h->opt.pfd_global || pfe::pfd_lds_bytes(in->nsub, in->proflen) > pfe::PFD_LDS_LIMIT;
+}
+static int pfd_shape_err(pfe_handle* h, const char* fn, const pfe_pfd_in* in) {
+  const pfe::PfdGlobalPlan p = pfe::pfd_global_plan(in->nsub, in->proflen, 1);
+  return set_err(h, PFE_EINVAL,
+                 "%s: nsub=%d proflen=%d unsupported: proflen <= %d and the per-fold vectors "
+                 "(6*proflen + 3.5*nsub doubles = %zu bytes) <= %zu bytes of LDS",
+                 fn, in->nsub, in->proflen, pfe::PFD_G_MAX_L, p.lds, pfe::PFD_LDS_LIMIT);
+}
 int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* chis,
                    double* lyon8, uint32_t* status, uint32_t flags) {
   if (!h) return PFE_EINVAL;
@@ -797,11 +814,12 @@ int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* 
     return set_err(h, PFE_EINVAL, "pfd_dmprof: null input array");
   if (in->npart < 1 || in->nsub < 1 || in->proflen < 2)
     return set_err(h, PFE_EINVAL, "pfd_dmprof: shape %dx%dx%d", in->npart, in->nsub, in->proflen);
-  if (pfe::pfd_lds_bytes(in->nsub, in->proflen) > 160 * 1024)
-    return set_err(h, PFE_EINVAL, "pfd_dmprof: nsub*proflen=%d exceeds the LDS-resident limit",
-                   in->nsub * in->proflen);
+  const bool useg = pfd_use_global(h, in);
+  if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
+    return pfd_shape_err(h, "pfd_dmprof", in);
   int rc = call_begin(h);
   if (rc) return rc;
+  const pfe::PfdGlobalPlan gp = useg ? pfe::pfd_global_plan(in->nsub, in->proflen, n) : pfe::PfdGlobalPlan();
   hipStream_t st = h->stream;
   pfe::PfdArgs a;
   a.npart = in->npart;
@@ -812,16 +830,18 @@ int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* 
   const size_t np = (size_t)n * in->npart * in->nsub * in->proflen;
   // split pipeline: two buffers of part sums, chunks of up to 4096 folds
   // (2 x 4096 x nsub x L doubles: 268 MB at 32 x 128)
-  const bool split = h->opt.pfd_split && h->fork.side[0] && pfe::pfd_split_ok(a);
+  const bool split = !useg && h->opt.pfd_split && h->fork.side[0] && pfe::pfd_split_ok(a);
   const int64_t chunk = n < 4096 ? n : 4096;
-  const size_t wsb = split ? align256(2 * (size_t)chunk * in->nsub * in->proflen * sizeof(double)) : 0;
+  // (or the slabs of the global-memory kernel)
+  const size_t wsb = split ? align256(2 * (size_t)chunk * in->nsub * in->proflen * sizeof(double))
+                           : align256(gp.bytes());
   size_t wsoff = 0;
   if (split) {
     for (hipEvent_t& v : h->pev)
       if (!v) PFE_HIP(h, hipEventCreateWithFlags(&v, hipEventDisableTiming));
   }
   if (flags & PFE_FLAG_DEVICE_PTRS) {
-    if (split) {
+    if (wsb) {
       rc = ensure_scratch(h, wsb);
       if (rc) return rc;
     }
@@ -864,6 +884,11 @@ int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* 
     off += lb;
     a.status = (uint32_t*)(base + off);
   }
+  if (useg) {
+    a.tg = (char*)h->scratch + wsoff;
+    a.gblocks = gp.blocks;
+    a.gstride = gp.stride;
+  }
   hipError_t e = split ? pfe::launch_pfd_dmprof_split(a, st, h->fork.side[0],
                                                       (double*)((char*)h->scratch + wsoff), chunk,
                                                       h->pev)
@@ -899,11 +924,12 @@ int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* 
   if (in->npart < 1 || in->nsub < 2 || in->proflen < 8 || in->proflen > 1024)
     return set_err(h, PFE_EINVAL, "pfd_bates22: shape %dx%dx%d unsupported", in->npart, in->nsub,
                    in->proflen);
-  if (pfe::pfd_lds_bytes(in->nsub, in->proflen) > 160 * 1024)
-    return set_err(h, PFE_EINVAL, "pfd_bates22: nsub*proflen=%d exceeds the LDS-resident limit",
-                   in->nsub * in->proflen);
+  const bool useg = pfd_use_global(h, in);
+  if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
+    return pfd_shape_err(h, "pfd_bates22", in);
   int rc = call_begin(h);
   if (rc) return rc;
+  const pfe::PfdGlobalPlan gp = useg ? pfe::pfd_global_plan(in->nsub, in->proflen, n) : pfe::PfdGlobalPlan();
   hipStream_t st = h->stream;
   pfe::PfdArgs a;
   a.npart = in->npart;
@@ -912,12 +938,13 @@ int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* 
   a.n = n;
   a.waves = h->opt.pfd_waves;
   const size_t work = pfe::pfd22_workspace_bytes(n, in->proflen);
+  const size_t gb = gp.bytes();  // the slabs of the global-memory kernel, after the workspace
   const size_t np = (size_t)n * in->npart * in->nsub * in->proflen;
   double* dout = out;
   uint32_t* dstat = status;
   size_t off = 0;
   if (flags & PFE_FLAG_DEVICE_PTRS) {
-    rc = ensure_scratch(h, work);
+    rc = ensure_scratch(h, align256(work) + gb);
     if (rc) return rc;
     a.profs = in->profs;
     a.subfreqs = in->subfreqs;
@@ -928,7 +955,7 @@ int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* 
     const size_t cb = align256((size_t)n * PFE_PFD_NSCAL * sizeof(double));
     const size_t ob = align256((size_t)n * 22 * sizeof(double));
     const size_t tb = align256((size_t)n * sizeof(uint32_t));
-    rc = ensure_scratch(h, pb + fb + cb + ob + tb + work);
+    rc = ensure_scratch(h, pb + fb + cb + ob + tb + align256(work) + gb);
     if (rc) return rc;
     char* base = (char*)h->scratch;
     PFE_HIP(h, hipMemcpyAsync(base, in->profs, np * sizeof(double), hipMemcpyHostToDevice, st));
@@ -946,6 +973,11 @@ int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* 
     off += ob;
     dstat = (uint32_t*)(base + off);
     off += tb;
+  }
+  if (useg) {
+    a.tg = (char*)h->scratch + off + align256(work);
+    a.gblocks = gp.blocks;
+    a.gstride = gp.stride;
   }
   hipError_t e = pfe::launch_pfd22(a, dout, dstat, (char*)h->scratch + off, work, st, &h->fork,
                                    h->opt);

@@ -20,6 +20,8 @@ struct Options {
   int pfd_split = 0;               // PFD dmprof: 1 part sums by k_pfd_parts beside the sweep, 0 fused
   int lyon8_dm_split = 1;          // DataBlock rows: 1 split last chunks + paired one-chunk rows,
                                    // 2 chain splits only, 0 one lane per leaf
+  int pfd_global = 0;              // PFD dmprof: 1 every shape on k_pfd_dmprof_g (the fold in global
+                                   // scratch), 0 only the shapes that do not fit the LDS
 };
 
 }  // namespace pfe

@@ -26,6 +26,11 @@ struct PfdArgs {
   // the folds' part sums T (n x nsub x L, k_pfd_parts) read from global memory instead of
   // reduced in the kernel (split pipeline), or null (fused)
   const double* tin = nullptr;
+  // k_pfd_dmprof_g: gblocks private slabs of gstride bytes each (pfd_global_plan) in device
+  // scratch, or null (the fold lives in LDS)
+  void* tg = nullptr;
+  int gblocks = 0;
+  size_t gstride = 0;
 };
 
 // split pipeline of pfe_pfd_dmprof: k_pfd_parts streams chunks of `chunk` folds' part sums
@@ -37,6 +42,21 @@ hipError_t launch_pfd_dmprof_split(const PfdArgs& a, hipStream_t st, hipStream_t
                                    int64_t chunk, hipEvent_t (&ev)[4]);
 
 size_t pfd_lds_bytes(int nsub, int L);
+constexpr size_t PFD_LDS_LIMIT = 160 * 1024;  // the LDS one workgroup can hold (gfx950)
+constexpr int PFD_G_MAX_L = 65535;            // k_pfd_dmprof_g keeps its rotations as uint16_t
+// k_pfd_dmprof_g keeps the fold in a slab of global scratch, so it takes every shape whose
+// per-fold vectors (lds bytes) fit on chip.  A launch over n folds runs `blocks` persistent
+// workgroups -- min(n, 2 x CUs, 1 GiB of slabs), at least one -- on blocks x stride bytes.
+struct PfdGlobalPlan {
+  size_t lds = 0;        // dynamic LDS of the kernel
+  size_t stride = 0;     // bytes per slab (a multiple of 256)
+  int blocks = 0;
+  bool rot_lds = false;  // the 100 x nsub rotation table in LDS (else behind the fold in the slab)
+  bool ok = false;       // false: proflen > PFD_G_MAX_L or lds > PFD_LDS_LIMIT
+  size_t bytes() const { return stride * (size_t)blocks; }
+};
+PfdGlobalPlan pfd_global_plan(int nsub, int L, int64_t n);
+hipError_t launch_pfd_dmprof_g(const PfdArgs& a, hipStream_t st);  // pfd_global.hip
 hipError_t launch_pfd_dmprof(const PfdArgs& a, hipStream_t st);
 // the 22-score chain (pfd22.hip); work: pfd22_workspace_bytes(n, L) bytes of device memory
 size_t pfd22_workspace_bytes(int64_t n, int L);

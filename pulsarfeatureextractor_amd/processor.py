@@ -35,6 +35,7 @@ import numpy as np
 from . import pfd as _pfd
 from . import phcx as _phcx
 from . import writers
+from ._native import PfeError
 from .candidate import GROUP_ERRORS, get_engine, status_error
 
 BATCH = 8192  # files per streamed batch
@@ -260,7 +261,12 @@ def score_pfd(datas, engine=None, batch: int = 1 << 14):
         for s0 in range(0, len(idx), batch):
             part = idx[s0:s0 + batch]
             profs, subfreqs, scal = _pfd.batch_inputs([datas[i] for i in part])
-            r = engine.pfd_dmprof(profs, subfreqs, scal, chis=False)
+            try:
+                r = engine.pfd_dmprof(profs, subfreqs, scal, chis=False)
+            except PfeError as e:  # a shape the library refuses fails its folds, not the run
+                for i in part:
+                    err[i] = f"Exception: {e}"
+                continue
             for j, i in enumerate(part):
                 profiles[i] = r["profile"][j]
                 if int(r["status"][j]) & 0x20:
@@ -283,7 +289,12 @@ def score_pfd22(datas, engine=None, batch: int = 1 << 16):
     for _shape, idx in groups.items():
         for s0 in range(0, len(idx), batch):
             part = idx[s0:s0 + batch]
-            o, st = engine.pfd_bates22(*_pfd.batch_inputs([datas[i] for i in part]))
+            try:
+                o, st = engine.pfd_bates22(*_pfd.batch_inputs([datas[i] for i in part]))
+            except PfeError as e:  # a shape the library refuses fails its folds, not the run
+                for i in part:
+                    err[i] = f"Exception: {e}"
+                continue
             for j, i in enumerate(part):
                 msg = status_error(int(st[j]))
                 if msg:
@@ -306,7 +317,12 @@ def pfd_profile_and_curve(datas, engine=None, batch: int = 1 << 14):
     for _shape, idx in groups.items():
         for s0 in range(0, len(idx), batch):
             part = idx[s0:s0 + batch]
-            r = engine.pfd_dmprof(*_pfd.batch_inputs([datas[i] for i in part]), lyon8=False)
+            try:
+                r = engine.pfd_dmprof(*_pfd.batch_inputs([datas[i] for i in part]), lyon8=False)
+            except PfeError as e:  # a shape the library refuses fails its folds, not the run
+                for i in part:
+                    err[i] = f"Exception: {e}"
+                continue
             for j, i in enumerate(part):
                 profiles[i] = r["profile"][j]
                 curves[i] = r["chis"][j]
@@ -832,8 +848,6 @@ class DataProcessor:
     def _bates_native(self, pre, mat, err, slot=0):
         """22 scores of the reader's good files: one pfe_phcx_pack per (shape, chunk) into
         pinned slabs, pfe_bates22 on them (DataProcessor.py:491-525 batched)."""
-        from ._native import PfeError
-
         info, px, sl = pre.info, pre.px, self._slab(slot)
         ok = np.flatnonzero(info["status"] == 0)
         keys = np.stack([info["lp"], info["nsub"], info["lsb"], info["ndm"]], 1)[ok]
@@ -938,9 +952,12 @@ class DataProcessor:
         if not datas:
             return
         if mode == "profile":       # PFDFile.computeProfileScores (:479-492)
-            _f, profiles, _e = score_pfd(datas, eng)
+            _f, profiles, errs = score_pfd(datas, eng)
             for j, k in enumerate(good):
-                res.rows[pf[k]] = np.asarray(profiles[j], dtype=np.float64)
+                if profiles[j] is None:  # the fold's shape was refused
+                    res.err[pf[k]] = errs[j]
+                else:
+                    res.rows[pf[k]] = np.asarray(profiles[j], dtype=np.float64)
         elif mode == "lyon8":
             feats, _prof, errs = score_pfd(datas, eng)
             for j, k in enumerate(good):
@@ -951,7 +968,8 @@ class DataProcessor:
                 prof, chis, derr = pfd_profile_and_curve(datas, eng)
                 for j, k in enumerate(good):
                     res.err[pf[k]] = errs[j] or derr[j]
-                    res.rows[pf[k]] = (sc[j], [float(v) for v in prof[j]], list(chis[j]))
+                    if prof[j] is not None:
+                        res.rows[pf[k]] = (sc[j], [float(v) for v in prof[j]], list(chis[j]))
             else:
                 for j, k in enumerate(good):
                     res.mat[pf[k]], res.err[pf[k]] = sc[j], errs[j]

@@ -177,8 +177,18 @@ int pfe_lyon8_u8(pfe_handle* h, const uint8_t* prof, int64_t prof_stride, int32_
                  const uint8_t* dm, int64_t dm_stride, int32_t ld, int64_t n, double* out,
                  uint32_t* status, uint32_t flags);
 
-/* Same with fp64 rows (PFD profiles are float; PFDFile.py:522-583).  Two-pass fp64
- * moments, as numpy/scipy compute them. */
+/* Same with fp64 rows (PFD profiles are float; PFDFile.py:522-583).  Two-pass fp64 moments
+ * summed in numpy's own order (8-accumulator leaves of <= 128 values, pairwise splits at
+ * floor8(n/2), rows longer than 8192 values in buffers of 8192), so for rows of any length,
+ * stride and 8-byte alignment:
+ *   mean, std, kurt (columns 0, 1, 3, 4, 5, 7) : the bits of numpy.mean, numpy.std and
+ *          scipy.stats.kurtosis evaluated as m4 / (m2 * m2) - 3, infinities included;
+ *   skew (columns 2, 6) : m3 / pow(m2, 1.5) with the device's pow, within 1e-13 relative of
+ *          scipy.stats.skew;
+ *   NaN exactly where scipy gives NaN: non-finite rows, and zero variance by scipy's rule
+ *          m2 <= (eps * mean)^2 -- a constant row of a value whose sum rounds is not always
+ *          one (numpy's mean may land an ulp off the value; scipy then returns skew = +-1,
+ *          kurt = -2, and so does this call). */
 int pfe_lyon8_f64(pfe_handle* h, const double* prof, int64_t prof_stride, int32_t lp,
                   const double* dm, int64_t dm_stride, int32_t ld, int64_t n, double* out,
                   uint32_t* status, uint32_t flags);

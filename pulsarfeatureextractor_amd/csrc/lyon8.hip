@@ -26,6 +26,7 @@
 //   * Generic path (any lengths/alignment): one wave per (candidate,row), byte loads,
 //     64-bit per-lane sums, 128-bit finalisation.
 
+#include "np_sum.h"
 #include "options.h"
 #include "pfe_common.h"
 
@@ -1386,44 +1387,38 @@ void lyon8_u8_dm(const uint8_t* __restrict__ prof, int64_t ps, const uint8_t* __
 }
 
 // ---- fp64 rows (PFD) -------------------------------------------------------------------
-// Two-pass fp64, as numpy/scipy: mean = sum/n; m_k = mean((x-mean)^k) with d^3 = d^2*d and
-// d^4 = (d^2)^2 (scipy.stats._moment exponentiation by squares).  One wave per row.
+// numpy.mean / numpy.std / scipy.stats.skew / kurtosis of float64 rows with numpy's own order
+// of additions (np_sum.h: the 8-accumulator leaf, the split at floor8(n / 2), a long row in
+// buffers of 8192 values), so mean, std and kurtosis are numpy's bits and the skew
+// m3 / pow(m2, 1.5) is within the device pow's last bits of scipy's.  Eight rows per wave,
+// one per group of 8 lanes (a leaf's 8 accumulators); a wave takes 8 profile rows or the 8
+// DM rows of the same candidates, so the length, and with it every split, is wave-uniform.
+// Rows are read from global memory twice (the sum, then the three sums of powers of
+// x - mean).  NC: both lengths <= np_inl_max(3) = 968, every level of the pairwise tree
+// inlined; else one call per level (254 VGPRs and a stack, one wave per SIMD: a first
+// correct version for rows that long).
+template <bool NC>
 __global__ __launch_bounds__(256) void lyon8_f64_generic(const double* __restrict__ prof,
                                                          int64_t ps, int lp,
                                                          const double* __restrict__ dm,
                                                          int64_t ds, int ld, int64_t n,
                                                          double* __restrict__ out) {
   const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t w = wave; w < 2 * n; w += nwaves) {
-    const int64_t c = w >> 1;
-    const int row = (int)(w & 1);
-    const double* p = row ? dm + c * ds : prof + c * ps;
+  const int g = lane >> 3, t = lane & 7;
+  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) +
+                       __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  const int64_t units = 2 * ((n + 7) >> 3);
+  for (int64_t u = wave; u < units; u += nwaves) {
+    const int row = (int)(u & 1);
+    const int64_t c = (u >> 1) * 8 + g;
+    const bool own = c < n;
+    const int64_t cr = own ? c : n - 1;  // idle groups redo the last row: every lane stays active
+    const double* p = row ? dm + cr * ds : prof + cr * ps;
     const int len = row ? ld : lp;
-    double s = 0.0;
-    for (int i = lane; i < len; i += 64) s += p[i];
-    s = wave_sum_f64(s);
-    const double mean = s / (double)len;
-    double a2 = 0.0, a3 = 0.0, a4 = 0.0;
-    for (int i = lane; i < len; i += 64) {
-      const double d = p[i] - mean;
-      const double d2 = d * d;
-      a2 += d2;
-      a3 += d2 * d;
-      a4 += d2 * d2;
-    }
-    a2 = wave_sum_f64(a2);
-    a3 = wave_sum_f64(a3);
-    a4 = wave_sum_f64(a4);
-    if (lane < 4) {
-      Moments m;
-      m.mean = mean;
-      m.m2 = a2 / (double)len;
-      m.m3 = a3 / (double)len;
-      m.m4 = a4 / (double)len;
-      out[c * 8 + row * 4 + lane] = stat_k(m, lane);
-    }
+    double o[4];
+    stats4_f64_g8<NC>(p, len, t, o);
+    if (own && t < 4) out[c * 8 + row * 4 + t] = t == 0 ? o[0] : t == 1 ? o[1] : t == 2 ? o[2] : o[3];
   }
 }
 
@@ -1714,8 +1709,11 @@ hipError_t launch_lyon8_f64(const double* prof, int64_t ps, int lp, const double
                             int64_t ds, int ld, int64_t n, double* out, hipStream_t st,
                             const Options& o) {
   if (n <= 0) return hipSuccess;
-  const int grid = grid_for(2 * n, o.lyon8_blocks);
-  hipLaunchKernelGGL(lyon8_f64_generic, dim3(grid), dim3(256), 0, st, prof, ps, lp, dm, ds, ld, n, out);
+  const int grid = grid_for(2 * ((n + 7) / 8), o.lyon8_blocks);  // a wave per 8 rows
+  if (lp <= np_inl_max(3) && ld <= np_inl_max(3))
+    hipLaunchKernelGGL(lyon8_f64_generic<true>, dim3(grid), dim3(256), 0, st, prof, ps, lp, dm, ds, ld, n, out);
+  else
+    hipLaunchKernelGGL(lyon8_f64_generic<false>, dim3(grid), dim3(256), 0, st, prof, ps, lp, dm, ds, ld, n, out);
   return hipGetLastError();
 }
 

@@ -114,13 +114,7 @@ __device__ __forceinline__ void stats4_f64(const double* x, double* tmp, int n, 
   lds_sync();
   const double m4 = np_sum_row<NC>(tmp, n, lane) / (double)n;
   lds_sync();
-  const double eps = 2.220446049250313e-16;
-  const double zl = eps * mean;
-  const bool zero = m2 <= zl * zl;
-  o[0] = mean;
-  o[1] = sqrt(m2);
-  o[2] = zero ? NAN : m3 / pow(m2, 1.5);
-  o[3] = zero ? NAN : m4 / (m2 * m2) - 3.0;
+  stats4_finish(mean, m2, m3, m4, o);
 }
 
 // the same in float32 (numpy on a float32 array): the element passes spread over the lanes,

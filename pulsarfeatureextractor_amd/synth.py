@@ -51,6 +51,64 @@ def lyon_batch(n: int, lp: int = 128, ld: int = 128, seed: int = BASE_SEED + 2,
     return prof, dm
 
 
+F64_EDGE_ROWS = 40
+
+
+def f64_edge_rows(L: int, rng: np.random.Generator):
+    """F64_EDGE_ROWS float64 rows of length L at the edges of the float-row Lyon path, and a
+    short name for each: ((40, L) float64, [names]).
+
+    Constant rows of a non-dyadic value (numpy's mean lands on the value or an ulp off it, so
+    scipy's zero-variance rule gives NaN or +-1.0 / -2.0 depending on the order of additions),
+    constant rows of an exact value, a one-ulp step, noise on a large offset (the last bit of
+    the mean moves every x - mean), a wide dynamic range, scales at which d^2 underflows and
+    d^4 overflows, a spike, +-1, a ramp, non-finite values, and plain noise to fill up."""
+    rows, names = [], []
+
+    def add(name, row):
+        names.append(name)
+        rows.append(np.asarray(row, dtype=np.float64).reshape(L))
+
+    ks = rng.choice(np.array([k for k in range(1, 255) if k % 3]), size=6, replace=False)
+    for k in ks:
+        add(f"const_{k}/3", np.full(L, k / 3.0))
+    for i, v in enumerate(rng.uniform(-300.0, 300.0, size=6)):
+        add(f"const_u{i}", np.full(L, v))
+    if L >= 3:
+        add("const_0.1", np.full(L, 0.1))
+        add("const_-253.7", np.full(L, -253.7))
+    for v in (0.0, 1.0, -2.5):
+        add(f"exact_{v}", np.full(L, v))
+    step = np.full(L, 3.0)
+    step[L // 2] = np.nextafter(3.0, np.inf)
+    add("step_1ulp", step)
+    add("offset_1e9", 1e9 + rng.normal(0.0, 1.0, L))
+    add("offset_-1e6", -1e6 + rng.normal(0.0, 1e-3, L))
+    add("wide", rng.normal(0.0, 1.0, L) * 10.0 ** rng.uniform(-8.0, 8.0, L))
+    add("scale_1e-160", rng.normal(0.0, 1.0, L) * 1e-160)
+    add("scale_1e160", rng.normal(0.0, 1.0, L) * 1e160)
+    spike = np.zeros(L)
+    spike[L // 3] = 1e6
+    add("spike", spike)
+    add("alternating", np.where(np.arange(L) % 2 == 0, 1.0, -1.0))
+    add("ramp", np.arange(L) / 7.0)
+    r = rng.normal(100.0, 10.0, L)
+    r[L // 2] = np.nan
+    add("nan", r)
+    r = rng.normal(100.0, 10.0, L)
+    r[L // 2] = np.inf
+    add("inf", r)
+    r = rng.normal(100.0, 10.0, L)
+    r[0] = np.inf
+    r[L - 1] = -np.inf
+    add("inf_-inf", r)
+    i = 0
+    while len(rows) < F64_EDGE_ROWS:
+        add(f"plain{i}", rng.normal(100.0, 10.0, L))
+        i += 1
+    return np.stack(rows), names
+
+
 def bates_batch(n: int, lp: int = 128, nsub: int = 16, lsb: int = 128, ndm: int = 128,
                 seed: int = BASE_SEED + 3):
     """Inputs of the 22-score path: profile, sub-bands, reduced DM curve and scalars.

@@ -267,6 +267,18 @@ int pfe_params4(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* st
 int pfe_dmfit4(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* status,
                uint32_t flags);
 
+/* The two profile groups on float profiles: the batched form of getSinusoidFittings /
+ * getGaussianFittings on the 0..255 float profile PFDFile hands them (PFDFile.py:658, :725).
+ *   prof : n dense rows of lp fp64 bins (8 <= lp <= 1024), host or device as the flags say
+ *   out  : n x 4 = s1-s4 (pfe_sinusoid4_f64) / n x 7 = s5-s11 (pfe_gauss7_f64)
+ * The kernels are those pfe_pfd_bates22 runs on its profile, so with `prof` the profile
+ * pfe_pfd_dmprof returns for a fold the values are the bits of columns 0-3 / 4-10 of
+ * pfe_pfd_bates22.  Status, pointers and scratch as pfe_sinusoid4 / pfe_gauss7. */
+int pfe_sinusoid4_f64(pfe_handle* h, const double* prof, int32_t lp, int64_t n, double* out,
+                      uint32_t* status, uint32_t flags);
+int pfe_gauss7_f64(pfe_handle* h, const double* prof, int32_t lp, int64_t n, double* out,
+                   uint32_t* status, uint32_t flags);
+
 /* ---- PFD (PRESTO fold) files: preprocessing + Lyon features -------------------------
  * pfe_pfd_dmprof <- what a freshly loaded PFDFile computes for the dmprof path
  *   dedisperse (PFDFile.py:330-374) at the best DM, getprofile + scale (:256-310),
@@ -318,6 +330,29 @@ int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* 
  * fits); within those, the shapes of pfe_pfd_dmprof (so every nsub <= 1024). */
 int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
                     uint32_t flags);
+
+/* One score group of a fold alone: the batched form of one method of PFDOperations.  Inputs,
+ * shape limits and PFE_EINVAL texts as pfe_pfd_bates22; the same kernels doing only the
+ * group's work, so every value is the bits of the group's columns of pfe_pfd_bates22, and
+ * status carries that group's failure bit only.
+ *   pfe_pfd_params4  <- getCandidateParameters(data)      PFDOperations.py:93-233
+ *                       out n x 4 = [period_ms, snr, dm, width] as the method returns them
+ *                       (PFDFile applies filterScore(13/14) for s13/s14); status 0.  No
+ *                       chi^2 sweep, no sub-band scores.
+ *   pfe_pfd_dmfit4   <- getDMFittings(data)               PFDOperations.py:274-393
+ *                       out n x 4 = [s16, s17, Shift, s19]: the method's signed Shift
+ *                       (s18 = |Shift|); PFE_ST_DMFIT_FAIL.  The sweep, the parameters the
+ *                       fit reads and the fit of PFE_OPT_SOLVER; no sub-band scores, no
+ *                       sine or Gaussian fit.
+ *   pfe_pfd_subband3 <- getSubbandParameters(data)        PFDOperations.py:401-466
+ *                       out n x 3 = s20-s22 (with the fold's own width);
+ *                       PFE_ST_SUBBAND_FAIL.  No sweep. */
+int pfe_pfd_params4(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
+                    uint32_t flags);
+int pfe_pfd_dmfit4(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
+                   uint32_t flags);
+int pfe_pfd_subband3(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
+                     uint32_t flags);
 
 #ifdef __cplusplus
 }

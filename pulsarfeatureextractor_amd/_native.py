@@ -47,8 +47,13 @@ EXPORTED_SYMBOLS = (
     "pfe_gauss7",
     "pfe_params4",
     "pfe_dmfit4",
+    "pfe_sinusoid4_f64",
+    "pfe_gauss7_f64",
     "pfe_pfd_dmprof",
     "pfe_pfd_bates22",
+    "pfe_pfd_params4",
+    "pfe_pfd_dmfit4",
+    "pfe_pfd_subband3",
 )
 PFE_PFD_NSCAL = 8
 PFE_PFD_NDM = 100
@@ -215,8 +220,12 @@ def load_library(path: str | None = None) -> C.CDLL:
             getattr(lib, g).argtypes = [vp, C.POINTER(BatesIn), vp, vp, u32]
         lib.pfe_pfd_dmprof.restype = C.c_int
         lib.pfe_pfd_dmprof.argtypes = [vp, C.POINTER(PfdIn), vp, vp, vp, vp, u32]
-        lib.pfe_pfd_bates22.restype = C.c_int
-        lib.pfe_pfd_bates22.argtypes = [vp, C.POINTER(PfdIn), vp, vp, u32]
+        for g in ("pfe_pfd_bates22", "pfe_pfd_params4", "pfe_pfd_dmfit4", "pfe_pfd_subband3"):
+            getattr(lib, g).restype = C.c_int
+            getattr(lib, g).argtypes = [vp, C.POINTER(PfdIn), vp, vp, u32]
+        for g in ("pfe_sinusoid4_f64", "pfe_gauss7_f64"):
+            getattr(lib, g).restype = C.c_int
+            getattr(lib, g).argtypes = [vp, vp, i32, i64, vp, vp, u32]
         pp = C.POINTER(C.c_char_p)
         lib.pfe_phcx_parse.restype = C.c_int
         lib.pfe_phcx_parse.argtypes = [pp, i64, i32, i32, C.POINTER(vp)]
@@ -586,6 +595,41 @@ class Engine:
         """getDMFittings (pfe_dmfit4): [peak, |1 - Prop|, Shift (signed), chi_theo]."""
         return self._group("pfe_dmfit4", 4, None, dmcurve, scal, out, status)
 
+    def _group_f64(self, fn, k, prof, out, status):
+        if prof.ndim != 2:
+            raise ValueError("prof must be (n, lp)")
+        n, lp = prof.shape
+        if _is_device(prof):
+            import torch
+
+            self._dev(prof, "prof", (torch.float64,))
+            self._follow_torch()
+            if out is None:
+                out = torch.empty((n, k), dtype=torch.float64, device=prof.device)
+            self._dev(out, "out", (torch.float64,), (n, k))
+            status = self._status_dev(status, n)
+            flags = PFE_FLAG_DEVICE_PTRS
+        else:
+            if not isinstance(prof, np.ndarray) or prof.dtype != np.float64:
+                raise TypeError(f"{fn}: float64 profile rows expected (byte profiles go through "
+                                "sinusoid4 / gauss7)")
+            prof = np.ascontiguousarray(prof)
+            out = self._out_host(out, n, k)
+            status = self._status_host(status, n)
+            flags = 0
+        self._check(getattr(self.lib, fn)(self._h, _ptr(prof), lp, n, _ptr(out), _ptr(status),
+                                          flags))
+        return out, status
+
+    def sinusoid4_f64(self, prof, out=None, status=None):
+        """getSinusoidFittings on float profiles (pfe_sinusoid4_f64): prof (n, lp) float64,
+        e.g. pfd_dmprof's profile -> ((n, 4) s1-s4, (n,) status)."""
+        return self._group_f64("pfe_sinusoid4_f64", 4, prof, out, status)
+
+    def gauss7_f64(self, prof, out=None, status=None):
+        """getGaussianFittings on float profiles (pfe_gauss7_f64) -> ((n, 7) s5-s11, status)."""
+        return self._group_f64("pfe_gauss7_f64", 7, prof, out, status)
+
     def features30(self, prof, lyon_dm, sub, dmcurve, scal, out=None):
         """Config 5's feature matrix: the 8 Lyon features (profile + Lyon DM rows) then the
         22 Bates scores of each candidate -> ((n, 30) float64, (n,) status)."""
@@ -658,27 +702,44 @@ class Engine:
         del keep
         return out
 
-    def pfd_bates22(self, profs, subfreqs, scal, out=None, status=None):
-        """The 22 scores of PFD folds (pfe_pfd_bates22, PFDFile.compute) for a batch of one
-        shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL) with
-        scal[:, 7] = bary_p1.  Returns (out (n,22) f64, status (n,))."""
-        pin, dev, keep = self._pfd_args(profs, subfreqs, scal, "pfd_bates22")
+    def _pfd_scores(self, fn, k, profs, subfreqs, scal, out, status):
+        pin, dev, keep = self._pfd_args(profs, subfreqs, scal, fn)
         n = pin.n
         if dev:
             import torch
 
             if out is None:
-                out = torch.empty((n, 22), dtype=torch.float64, device=profs.device)
-            self._dev(out, "out", (torch.float64,), (n, 22))
+                out = torch.empty((n, k), dtype=torch.float64, device=profs.device)
+            self._dev(out, "out", (torch.float64,), (n, k))
             status = self._status_dev(status, n)
             flags = PFE_FLAG_DEVICE_PTRS
         else:
-            out = self._out_host(out, n, 22)
+            out = self._out_host(out, n, k)
             status = self._status_host(status, n)
             flags = 0
-        self._check(self.lib.pfe_pfd_bates22(self._h, C.byref(pin), _ptr(out), _ptr(status), flags))
+        self._check(getattr(self.lib, "pfe_" + fn)(self._h, C.byref(pin), _ptr(out), _ptr(status),
+                                                   flags))
         del keep
         return out, status
+
+    def pfd_bates22(self, profs, subfreqs, scal, out=None, status=None):
+        """The 22 scores of PFD folds (pfe_pfd_bates22, PFDFile.compute) for a batch of one
+        shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL) with
+        scal[:, 7] = bary_p1.  Returns (out (n,22) f64, status (n,))."""
+        return self._pfd_scores("pfd_bates22", 22, profs, subfreqs, scal, out, status)
+
+    # one score group of a batch of folds (PFDOperations; inputs as pfd_bates22)
+    def pfd_params4(self, profs, subfreqs, scal, out=None, status=None):
+        """getCandidateParameters (pfe_pfd_params4): [period_ms, snr, dm, width], unfiltered."""
+        return self._pfd_scores("pfd_params4", 4, profs, subfreqs, scal, out, status)
+
+    def pfd_dmfit4(self, profs, subfreqs, scal, out=None, status=None):
+        """getDMFittings (pfe_pfd_dmfit4): [s16, s17, Shift (signed), s19]."""
+        return self._pfd_scores("pfd_dmfit4", 4, profs, subfreqs, scal, out, status)
+
+    def pfd_subband3(self, profs, subfreqs, scal, out=None, status=None):
+        """getSubbandParameters (pfe_pfd_subband3): s20-s22."""
+        return self._pfd_scores("pfd_subband3", 3, profs, subfreqs, scal, out, status)
 
 
 class PhcxBatch:

@@ -21,7 +21,7 @@ import numpy as np
 from . import pfd as _pfd
 from . import phcx as _phcx
 from ._native import (PFE_ST_DMFIT_FAIL, PFE_ST_GAUSS_FAIL, PFE_ST_SINE_FAIL,
-                      PFE_ST_SUBBAND_FAIL, Engine)
+                      PFE_ST_SUBBAND_FAIL, Engine, PfeError)
 
 _engine = None
 _engine_lock = threading.Lock()
@@ -115,6 +115,36 @@ class CandidateFileInterface:
     def isValid(self):
         raise NotImplementedError("Please Implement this method")
 
+    # one score group each (:173-194); compute() of the reference is these five calls
+    def computeSinusoidFittingScores(self):
+        raise NotImplementedError("Please Implement this method")
+
+    def computeGaussianFittingScores(self):
+        raise NotImplementedError("Please Implement this method")
+
+    def computeCandidateParameterScores(self):
+        raise NotImplementedError("Please Implement this method")
+
+    def computeDMCurveFittingScores(self):
+        raise NotImplementedError("Please Implement this method")
+
+    def computeSubBandScores(self):
+        raise NotImplementedError("Please Implement this method")
+
+    def _append_group(self, text, values, filtered=()):
+        """What every compute*Scores method of the reference does with its group: append the
+        values as floats -- through filterScore for the score numbers in `filtered`, given as
+        (index in values, score number) -- and turn anything raised into the group's text."""
+        try:
+            vals = [float(v) for v in values()]
+            for i, score in filtered:
+                vals[i] = self.filterScore(score, vals[i])
+        except PfeError:  # the library itself failed: not a property of the candidate
+            raise
+        except Exception:
+            raise Exception(text) from None
+        self.scores.extend(vals)
+
 
 class PHCXFile(CandidateFileInterface):
     """PHCXFile.PHCX (gzip, section 1); SUPERBPHCXFile subclasses with superb=True."""
@@ -127,6 +157,9 @@ class PHCXFile(CandidateFileInterface):
         self.profileIndex = 0 if self.SUPERB else 1
         self.scores = []
         self._engine = engine
+        from .profile_ops import PHCXOperations  # (profile_ops imports this module)
+
+        self.profileOps = PHCXOperations(debugFlag, engine=engine)
         self.setNumberOfScores(22)
         self.load()
 
@@ -161,6 +194,43 @@ class PHCXFile(CandidateFileInterface):
         """PHCXFile.compute (:383-409): the 22 scores."""
         self.scores = self._bates()
         return self.scores
+
+    # the five groups of compute(), one libpfe group call each (:413-668): each appends its
+    # scores to self.scores or raises its group's text
+    def computeSinusoidFittingScores(self):
+        """:413-470 -- s1-s4 (pfe_sinusoid4)."""
+        self._append_group("Sinusoid fitting exception",
+                           lambda: self.profileOps.getSinusoidFittings(self.profile))
+
+    def computeGaussianFittingScores(self):
+        """:475-543 -- s5-s11 (pfe_gauss7)."""
+        self._append_group("Gaussian fitting exception",
+                           lambda: self.profileOps.getGaussianFittings(self.profile))
+
+    def computeCandidateParameterScores(self):
+        """:547-585 -- s12-s15 (pfe_params4), s13 / s14 through filterScore."""
+        self._append_group(
+            "Candidate parameters exception",
+            lambda: self.profileOps.getCandidateParameters(self.data, self.profileIndex),
+            ((1, 13), (2, 14)))
+
+    def computeDMCurveFittingScores(self):
+        """:589-629 -- s16-s19 (pfe_dmfit4), s18 through filterScore."""
+        self._append_group(
+            "DM curve fitting exception",
+            lambda: self.profileOps.getDMFittings(self.data, self.profileIndex), ((2, 18),))
+
+    def computeSubBandScores(self):
+        """:633-668 -- s20-s22 (pfe_subband3)."""
+        self._append_group(
+            "Subband scoring exception",
+            lambda: self.profileOps.getSubbandParameters(self.profileIndex, self.data,
+                                                         self.profile))
+
+    def getDMPlaneCurveData(self):
+        """:672-684 -- the candidate's DM curve as a list: the reduced curve of the scored
+        section's DataBlock (PHCXOperations.dm_curve), which the parser already holds."""
+        return [float(v) for v in self.data.dm_curve]
 
     def computeProfileScores(self):
         """:291-304 — the profile bins as float scores (--profile)."""
@@ -211,6 +281,9 @@ class PFDFile(CandidateFileInterface):
         super().__init__(debugFlag)
         self.cand = candidateName
         self.engine = engine or get_engine()
+        from .profile_ops import PFDOperations  # (profile_ops imports this module)
+
+        self.profileOps = PFDOperations(debugFlag, engine=self.engine)
         self.data = _pfd.read(candidateName)
         self.scores = []
 
@@ -239,6 +312,34 @@ class PFDFile(CandidateFileInterface):
             raise Exception(msg)
         self.scores = [float(v) for v in out[0]]
         return self.scores
+
+    # the five groups of compute(), one libpfe group call each (:617-873).  The fold is parsed
+    # once (self.data) and one pfe_pfd_dmprof launch gives the profile of both profile groups
+    def computeSinusoidFittingScores(self):
+        """:617-674 -- s1-s4 (pfe_sinusoid4_f64 on the 0..255 float profile)."""
+        self._append_group("Sinusoid fitting exception",
+                           lambda: self.profileOps.getSinusoidFittings(self.getProfile()))
+
+    def computeGaussianFittingScores(self):
+        """:679-747 -- s5-s11 (pfe_gauss7_f64)."""
+        self._append_group("Gaussian fitting exception",
+                           lambda: self.profileOps.getGaussianFittings(self.getProfile()))
+
+    def computeCandidateParameterScores(self):
+        """:751-790 -- s12-s15 (pfe_pfd_params4), s13 / s14 through filterScore."""
+        self._append_group("Candidate parameters exception",
+                           lambda: self.profileOps.getCandidateParameters(self),
+                           ((1, 13), (2, 14)))
+
+    def computeDMCurveFittingScores(self):
+        """:794-834 -- s16-s19 (pfe_pfd_dmfit4), s18 through filterScore."""
+        self._append_group("DM curve fitting exception",
+                           lambda: self.profileOps.getDMFittings(self), ((2, 18),))
+
+    def computeSubBandScores(self):
+        """:838-873 -- s20-s22 (pfe_pfd_subband3; the profile is the fold's own)."""
+        self._append_group("Subband scoring exception",
+                           lambda: self.profileOps.getSubbandParameters(self))
 
     def computeProfileScores(self):
         """:479-492 — the 0..255 profile bins."""

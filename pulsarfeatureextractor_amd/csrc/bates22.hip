@@ -154,17 +154,20 @@ hipError_t fork_end(const Fork* fk, hipStream_t st) {
 // The score groups `groups` (BG_*) of the chain, each into its own columns of out (n x 22);
 // status gets the failure bits of those groups only.  raw_dm: getDMFittings' signed shift in
 // column 17 (the per-group entry point pfe_dmfit4) instead of the 22-score vector's |shift|.
+// fprof: the profiles as n x lp doubles (a PFD's float profile: the F = true kernels that
+// launch_pfd22 runs) instead of in->prof, or null.
 hipError_t launch_bates_groups(const pfe_bates_in* in, double* out, uint32_t* status, void* work,
                                size_t work_bytes, hipStream_t st, const Fork* fk,
-                               const Options& o, unsigned groups, bool raw_dm) {
+                               const Options& o, unsigned groups, bool raw_dm,
+                               const double* fprof) {
   if (work_bytes < bates22_workspace_bytes(in)) return hipErrorInvalidValue;
   BatesArgs a;
   bates_setup(a, in->n, in->lp, work, o);
   a.raw_dm = raw_dm ? 1 : 0;
   if (subband_work_bytes(in->n, in->nsub, in->lsb))
     a.sub_work = (void*)(((uintptr_t)work + bates22_core_bytes(in) + 255) & ~(uintptr_t)255);
-  a.prof = in->prof;
-  a.fprof = nullptr;
+  a.prof = fprof ? nullptr : in->prof;
+  a.fprof = fprof;
   a.lp = in->lp;
   a.sub = in->sub;
   a.nsub = in->nsub;
@@ -199,7 +202,7 @@ hipError_t launch_bates_groups(const pfe_bates_in* in, double* out, uint32_t* st
 
 hipError_t launch_bates22(const pfe_bates_in* in, double* out, uint32_t* status, void* work,
                           size_t work_bytes, hipStream_t st, const Fork* fk, const Options& o) {
-  return launch_bates_groups(in, out, status, work, work_bytes, st, fk, o, BG_ALL, false);
+  return launch_bates_groups(in, out, status, work, work_bytes, st, fk, o, BG_ALL, false, nullptr);
 }
 
 }  // namespace pfe

@@ -31,7 +31,8 @@ hipError_t launch_bates22(const pfe_bates_in* in, double* out, uint32_t* status,
 size_t bates22_workspace_bytes(const pfe_bates_in* in);
 hipError_t launch_bates_groups(const pfe_bates_in* in, double* out, uint32_t* status, void* work,
                                size_t work_bytes, hipStream_t st, const Fork* fk,
-                               const Options& o, unsigned groups, bool raw_dm);
+                               const Options& o, unsigned groups, bool raw_dm,
+                               const double* fprof);
 hipError_t launch_subband3(const pfe_bates_in* in, double* out, uint32_t* status, void* work,
                            hipStream_t st);
 const char* subband_shape_error(int nsub, int lsb);
@@ -641,10 +642,11 @@ int pfe_subband3(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* s
 }  // extern "C"
 
 // ---- one score group of the chain (ProfileOperationsInterface.py:69-130) ----------------
-// columns [c0, c0 + k) of the 22-score vector -> dst (n x k)
-__global__ void k_take_cols(const double* src, int c0, int k, int64_t n, double* dst) {
+// columns [c0, c0 + k) of the rows of src (n x ld: the 22-score vector, or the 8 DM-fit
+// inputs of the PFD path) -> dst (n x k)
+__global__ void k_take_cols(const double* src, int ld, int c0, int k, int64_t n, double* dst) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n * k) dst[i] = src[(i / k) * 22 + c0 + i % k];
+  if (i < n * k) dst[i] = src[(i / k) * ld + c0 + i % k];
 }
 
 // getCandidateParameters: (period, snr, dm, width) of each candidate, unfiltered
@@ -659,9 +661,12 @@ __global__ void k_params4(const double* scal, int64_t n, double* out, uint32_t* 
   status[i] = 0;
 }
 
-// groups: pfe::BG_SINE (cols 0-3) / BG_GAUSS (4-10) / BG_DM (15-18, raw shift)
+// groups: pfe::BG_SINE (cols 0-3) / BG_GAUSS (4-10) / BG_DM (15-18, raw shift).  f64: the
+// profile rows are in->n x in->lp doubles at fprof (the float profile of a PFD), in->prof and
+// in->scal are not read
 static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* status,
-                            uint32_t flags, const char* fn, unsigned groups, int c0, int k) {
+                            uint32_t flags, const char* fn, unsigned groups, int c0, int k,
+                            bool f64 = false, const double* fprof = nullptr) {
   if (!h) return PFE_EINVAL;
   h->err.clear();
   if (!in || !out || !status) return set_err(h, PFE_EINVAL, "%s: null argument", fn);
@@ -669,7 +674,7 @@ static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, 
   if (n < 0) return set_err(h, PFE_EINVAL, "%s: n < 0", fn);
   if (n == 0) return PFE_OK;
   const bool dm = groups == pfe::BG_DM;
-  if (!in->scal || (dm ? !in->dmcurve : !in->prof))
+  if (f64 ? !fprof : (!in->scal || (dm ? !in->dmcurve : !in->prof)))
     return set_err(h, PFE_EINVAL, "%s: null input array", fn);
   if (!dm && (in->lp < 8 || in->lp > 1024))
     return set_err(h, PFE_EINVAL, "%s: lp=%d outside [8,1024]", fn, in->lp);
@@ -682,6 +687,7 @@ static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, 
   pfe_bates_in g = *in;
   g.sub = nullptr;
   g.nsub = g.lsb = 0;
+  if (f64) g.prof = nullptr;
   if (dm) {
     g.prof = nullptr;
     g.lp = 0;
@@ -691,9 +697,10 @@ static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, 
   }
   const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
   const size_t work = pfe::bates22_workspace_bytes(&g);
-  const size_t pb = host && !dm ? align256((size_t)n * g.lp) : 0;
+  const size_t psz = f64 ? sizeof(double) : 1;  // bytes per profile bin
+  const size_t pb = host && !dm ? align256((size_t)n * g.lp * psz) : 0;
   const size_t db = host && dm ? align256((size_t)n * g.ndm * sizeof(double)) : 0;
-  const size_t cb = host ? align256((size_t)n * PFE_NSCAL * sizeof(double)) : 0;
+  const size_t cb = host && !f64 ? align256((size_t)n * PFE_NSCAL * sizeof(double)) : 0;
   const size_t ob = align256((size_t)n * 22 * sizeof(double));
   const size_t kb = host ? align256((size_t)n * k * sizeof(double)) : 0;
   const size_t tb = host ? align256((size_t)n * sizeof(uint32_t)) : 0;
@@ -707,14 +714,19 @@ static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, 
       PFE_HIP(h, hipMemcpyAsync(base, in->dmcurve, (size_t)n * g.ndm * sizeof(double),
                                 hipMemcpyHostToDevice, st));
       din.dmcurve = (const double*)base;
+    } else if (f64) {
+      PFE_HIP(h, hipMemcpyAsync(base, fprof, (size_t)n * g.lp * psz, hipMemcpyHostToDevice, st));
+      fprof = (const double*)base;
     } else {
       PFE_HIP(h, hipMemcpyAsync(base, in->prof, (size_t)n * g.lp, hipMemcpyHostToDevice, st));
       din.prof = (const uint8_t*)base;
     }
     off = pb + db;
-    PFE_HIP(h, hipMemcpyAsync(base + off, in->scal, (size_t)n * PFE_NSCAL * sizeof(double),
-                              hipMemcpyHostToDevice, st));
-    din.scal = (const double*)(base + off);
+    if (!f64) {
+      PFE_HIP(h, hipMemcpyAsync(base + off, in->scal, (size_t)n * PFE_NSCAL * sizeof(double),
+                                hipMemcpyHostToDevice, st));
+      din.scal = (const double*)(base + off);
+    }
     off += cb;
   }
   double* d22 = (double*)(base + off);
@@ -724,10 +736,10 @@ static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, 
   uint32_t* dst = host ? (uint32_t*)(base + off) : status;
   off += tb;
   hipError_t e = pfe::launch_bates_groups(&din, d22, dst, base + off, work, st, &h->fork, h->opt,
-                                          groups, dm);
+                                          groups, dm, f64 ? fprof : nullptr);
   if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
   hipLaunchKernelGGL(k_take_cols, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st, d22,
-                     c0, k, n, dk);
+                     22, c0, k, n, dk);
   PFE_HIP(h, hipGetLastError());
   if (host) {
     PFE_HIP(h, hipMemcpyAsync(out, dk, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -752,6 +764,28 @@ int pfe_gauss7(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* sta
 int pfe_dmfit4(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* status,
                uint32_t flags) {
   return bates_group_call(h, in, out, status, flags, "dmfit4", pfe::BG_DM, 15, 4);
+}
+
+// the float profile of a PFD (pfe_pfd_dmprof's `profile`) through the same kernels
+static int bates_group_call_f64(pfe_handle* h, const double* prof, int32_t lp, int64_t n,
+                                double* out, uint32_t* status, uint32_t flags, const char* fn,
+                                unsigned groups, int c0, int k) {
+  pfe_bates_in in{};
+  in.lp = lp;
+  in.n = n;
+  return bates_group_call(h, &in, out, status, flags, fn, groups, c0, k, true, prof);
+}
+
+int pfe_sinusoid4_f64(pfe_handle* h, const double* prof, int32_t lp, int64_t n, double* out,
+                      uint32_t* status, uint32_t flags) {
+  return bates_group_call_f64(h, prof, lp, n, out, status, flags, "sinusoid4_f64", pfe::BG_SINE,
+                              0, 4);
+}
+
+int pfe_gauss7_f64(pfe_handle* h, const double* prof, int32_t lp, int64_t n, double* out,
+                   uint32_t* status, uint32_t flags) {
+  return bates_group_call_f64(h, prof, lp, n, out, status, flags, "gauss7_f64", pfe::BG_GAUSS, 4,
+                              7);
 }
 
 int pfe_params4(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* status,
@@ -911,22 +945,26 @@ int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* 
   return call_end(h);
 }
 
-int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
-                    uint32_t flags) {
+}  // extern "C"
+
+// pfe_pfd_bates22 (groups = PFD_G_ALL: out n x 22) and the PFD group calls (one group: its k
+// columns from column c0 of the 22-score vector, or of the DM-fit inputs par22 when c0 < 0)
+static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
+                           uint32_t flags, const char* fn, unsigned groups, int c0, int k) {
   if (!h) return PFE_EINVAL;
   h->err.clear();
-  if (!in || !out || !status) return set_err(h, PFE_EINVAL, "pfd_bates22: null argument");
+  if (!in || !out || !status) return set_err(h, PFE_EINVAL, "%s: null argument", fn);
   const int64_t n = in->n;
-  if (n < 0) return set_err(h, PFE_EINVAL, "pfd_bates22: n < 0");
+  if (n < 0) return set_err(h, PFE_EINVAL, "%s: n < 0", fn);
   if (n == 0) return PFE_OK;
   if (!in->profs || !in->subfreqs || !in->scal)
-    return set_err(h, PFE_EINVAL, "pfd_bates22: null input array");
+    return set_err(h, PFE_EINVAL, "%s: null input array", fn);
   if (in->npart < 1 || in->nsub < 2 || in->proflen < 8 || in->proflen > 1024)
-    return set_err(h, PFE_EINVAL, "pfd_bates22: shape %dx%dx%d unsupported", in->npart, in->nsub,
+    return set_err(h, PFE_EINVAL, "%s: shape %dx%dx%d unsupported", fn, in->npart, in->nsub,
                    in->proflen);
   const bool useg = pfd_use_global(h, in);
   if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
-    return pfd_shape_err(h, "pfd_bates22", in);
+    return pfd_shape_err(h, fn, in);
   int rc = call_begin(h);
   if (rc) return rc;
   const pfe::PfdGlobalPlan gp = useg ? pfe::pfd_global_plan(in->nsub, in->proflen, n) : pfe::PfdGlobalPlan();
@@ -937,14 +975,18 @@ int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* 
   a.L = in->proflen;
   a.n = n;
   a.waves = h->opt.pfd_waves;
-  const size_t work = pfe::pfd22_workspace_bytes(n, in->proflen);
+  const bool all = groups == pfe::PFD_G_ALL;
+  const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
+  const size_t work = pfe::pfd22_workspace_bytes(n, in->proflen, groups);
   const size_t gb = gp.bytes();  // the slabs of the global-memory kernel, after the workspace
   const size_t np = (size_t)n * in->npart * in->nsub * in->proflen;
+  // a group call scores into a 22-column scratch of its own and hands out its k columns
+  const size_t sb = all ? 0 : align256((size_t)n * 22 * sizeof(double));
   double* dout = out;
   uint32_t* dstat = status;
   size_t off = 0;
-  if (flags & PFE_FLAG_DEVICE_PTRS) {
-    rc = ensure_scratch(h, align256(work) + gb);
+  if (!host) {
+    rc = ensure_scratch(h, sb + align256(work) + gb);
     if (rc) return rc;
     a.profs = in->profs;
     a.subfreqs = in->subfreqs;
@@ -953,9 +995,9 @@ int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* 
     const size_t pb = align256(np * sizeof(double));
     const size_t fb = align256((size_t)n * in->nsub * sizeof(double));
     const size_t cb = align256((size_t)n * PFE_PFD_NSCAL * sizeof(double));
-    const size_t ob = align256((size_t)n * 22 * sizeof(double));
+    const size_t ob = align256((size_t)n * k * sizeof(double));
     const size_t tb = align256((size_t)n * sizeof(uint32_t));
-    rc = ensure_scratch(h, pb + fb + cb + ob + tb + align256(work) + gb);
+    rc = ensure_scratch(h, pb + fb + cb + ob + tb + sb + align256(work) + gb);
     if (rc) return rc;
     char* base = (char*)h->scratch;
     PFE_HIP(h, hipMemcpyAsync(base, in->profs, np * sizeof(double), hipMemcpyHostToDevice, st));
@@ -974,20 +1016,53 @@ int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* 
     dstat = (uint32_t*)(base + off);
     off += tb;
   }
+  double* d22 = all ? dout : (double*)((char*)h->scratch + off);
+  off += sb;
   if (useg) {
     a.tg = (char*)h->scratch + off + align256(work);
     a.gblocks = gp.blocks;
     a.gstride = gp.stride;
   }
-  hipError_t e = pfe::launch_pfd22(a, dout, dstat, (char*)h->scratch + off, work, st, &h->fork,
-                                   h->opt);
-  if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "pfd_bates22 launch: %s", hipGetErrorString(e));
-  if (!(flags & PFE_FLAG_DEVICE_PTRS)) {
-    PFE_HIP(h, hipMemcpyAsync(out, dout, (size_t)n * 22 * sizeof(double), hipMemcpyDeviceToHost, st));
+  char* wk = (char*)h->scratch + off;
+  hipError_t e = pfe::launch_pfd22(a, d22, dstat, wk, work, st, &h->fork, h->opt, groups, !all);
+  if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
+  if (!all) {
+    const double* par22 = c0 < 0 ? pfe::pfd22_params(wk) : nullptr;
+    hipLaunchKernelGGL(k_take_cols, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st,
+                       c0 < 0 ? par22 : d22, c0 < 0 ? 8 : 22, c0 < 0 ? 0 : c0, k, n, dout);
+    PFE_HIP(h, hipGetLastError());
+  }
+  if (host) {
+    PFE_HIP(h, hipMemcpyAsync(out, dout, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, st));
     PFE_HIP(h, hipMemcpyAsync(status, dstat, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     PFE_HIP(h, hipStreamSynchronize(st));
   }
   return call_end(h);
+}
+
+extern "C" {
+
+int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
+                    uint32_t flags) {
+  return pfd_scores_call(h, in, out, status, flags, "pfd_bates22", pfe::PFD_G_ALL, 0, 22);
+}
+
+// [period_ms, snr, dm, width] as getCandidateParameters returns them: par22's first columns
+int pfe_pfd_params4(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
+                    uint32_t flags) {
+  return pfd_scores_call(h, in, out, status, flags, "pfd_params4", pfe::PFD_G_PARAMS, -1, 4);
+}
+
+int pfe_pfd_dmfit4(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
+                   uint32_t flags) {
+  return pfd_scores_call(h, in, out, status, flags, "pfd_dmfit4",
+                         pfe::PFD_G_PARAMS | pfe::PFD_G_DM, 15, 4);
+}
+
+int pfe_pfd_subband3(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
+                     uint32_t flags) {
+  return pfd_scores_call(h, in, out, status, flags, "pfd_subband3",
+                         pfe::PFD_G_PARAMS | pfe::PFD_G_SUB, 19, 3);
 }
 
 }  // extern "C"

@@ -8,6 +8,11 @@
 
 namespace pfe {
 
+// score groups of the 22-score path that a PFD launch serves (PfdArgs::groups): the candidate
+// parameters (s12-s15, which the other two read), the DM-curve fit (s16-s19) and the
+// sub-band scores (s20-s22)
+enum : unsigned { PFD_G_PARAMS = 1u, PFD_G_DM = 2u, PFD_G_SUB = 4u, PFD_G_ALL = 7u };
+
 struct PfdArgs {
   const double* profs;     // n x npart x nsub x L
   const double* subfreqs;  // n x nsub
@@ -22,6 +27,10 @@ struct PfdArgs {
   // DM-fit inputs [period, snr, dm, width, dm_start, dm_end] into par22 (n x 8); both or none
   double* out22 = nullptr;
   double* par22 = nullptr;
+  // the groups the caller wants of out22 (pfe_pfd_params4 / _dmfit4 / _subband3 ask for one):
+  // without PFD_G_SUB the sub-band scores are not computed (columns 19-21 are 0), without
+  // PFD_G_DM a fold with numdms == 1 is not marked (nothing reads its DM curve)
+  unsigned groups = PFD_G_ALL;
   int waves = 4;  // handle option PFE_OPT_PFD_WAVES: the four-wave kernel (<= 128 bins) or one wave
   // the folds' part sums T (n x nsub x L, k_pfd_parts) read from global memory instead of
   // reduced in the kernel (split pipeline), or null (fused)
@@ -58,10 +67,16 @@ struct PfdGlobalPlan {
 PfdGlobalPlan pfd_global_plan(int nsub, int L, int64_t n);
 hipError_t launch_pfd_dmprof_g(const PfdArgs& a, hipStream_t st);  // pfd_global.hip
 hipError_t launch_pfd_dmprof(const PfdArgs& a, hipStream_t st);
-// the 22-score chain (pfd22.hip); work: pfd22_workspace_bytes(n, L) bytes of device memory
-size_t pfd22_workspace_bytes(int64_t n, int L);
+// the 22-score chain (pfd22.hip); work: pfd22_workspace_bytes(n, L, groups) bytes of device
+// memory.  groups != PFD_G_ALL: only those groups' kernels run and only their columns of out
+// (n x 22) and their status bits are set; raw_dm: getDMFittings' signed shift in column 17
+size_t pfd22_workspace_bytes(int64_t n, int L, unsigned groups = PFD_G_ALL);
+// the DM-fit inputs par22 (n x 8: [period, snr, dm, width, ...], unfiltered) that a launch
+// without PFD_G_DM leaves in its workspace
+const double* pfd22_params(const void* work);
 struct Fork;
 hipError_t launch_pfd22(PfdArgs a, double* out, uint32_t* status, void* work, size_t work_bytes,
-                        hipStream_t st, const Fork* fk, const Options& o);
+                        hipStream_t st, const Fork* fk, const Options& o,
+                        unsigned groups = PFD_G_ALL, bool raw_dm = false);
 
 }  // namespace pfe

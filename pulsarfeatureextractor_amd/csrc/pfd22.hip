@@ -8,6 +8,8 @@
 //   k_sine<F>                 s1-s4 on the float profile        (bates_sine_dm_sub.hip)
 //   k_ghist<F>, k_gt1b, k_gdgb, k_gdg8b   s5-s11                (bates_gauss.hip)
 //   k_pfd_dmfitb              s16-s19: the clamped 4-parameter DM-curve fit (below)
+// One group alone (pfe_pfd_params4 / _dmfit4 / _subband3): launch_pfd22 with a group mask
+// runs k_pfd_dmprof for that group only, and the DM fit only for PFD_G_DM.
 #include <cmath>
 
 #include "bates_common.h"
@@ -198,7 +200,7 @@ __global__ __launch_bounds__(64) void k_pfd_dmfitb(PfdDMArgs d) {
       double* o = a.out + c * 22;
       o[15] = snr / sqrt((period - sqrt(wint)) / sqrt(wint));          // s16 (:346)
       o[16] = fabs(1.0 - S.x[1][f]);                                   // s17 (:391)
-      o[17] = fabs(S.x[2][f]);                                         // s18, filterScore(18)
+      o[17] = a.raw_dm ? S.x[2][f] : fabs(S.x[2][f]);                  // s18, filterScore(18)
       o[18] = ndeg ? chi / (double)ndeg : 0.0;                         // s19 (:387)
       if (!ndeg) atomicOr(&a.status[c], (uint32_t)(PFE_ST_DMFIT_FAIL));                     // ZeroDivisionError
     }
@@ -243,7 +245,7 @@ __device__ __forceinline__ void pfd_dm_finish(const PfdDMArgs& d, int64_t c, dou
     double* o = a.out + c * 22;
     o[15] = snr / sqrt((period - sqrt(wint)) / sqrt(wint));          // s16 (:346)
     o[16] = fabs(1.0 - prop);                                        // s17 (:391)
-    o[17] = fabs(shift);                                             // s18, filterScore(18)
+    o[17] = a.raw_dm ? shift : fabs(shift);                          // s18, filterScore(18)
     o[18] = ndeg ? chi / (double)ndeg : 0.0;                         // s19 (:387)
     if (!ndeg) atomicOr(&a.status[c], (uint32_t)(PFE_ST_DMFIT_FAIL));                     // ZeroDivisionError
   }
@@ -322,11 +324,13 @@ __global__ __launch_bounds__(64, 2) void k_pfd_dmfitg(PfdDMArgs d) {
   glm_engine<4, 4 * MPL, FPW>(prob, S, T.ph, T.list, d.a.hand[HAND_DM], HAND_K_DM);
 }
 
-size_t pfd22_workspace_bytes(int64_t n, int L) {
+size_t pfd22_workspace_bytes(int64_t n, int L, unsigned groups) {
   pfe_bates_in in{};
   in.n = n;
   in.lp = L;
   const size_t al = 255;
+  // the parameters or the sub-band scores alone: par22 and no fit
+  if (!(groups & PFD_G_DM)) return ((size_t)n * 8 * sizeof(double) + al) + 256;
   return bates22_workspace_bytes(&in) + ((size_t)n * L * sizeof(double) + al) +
          ((size_t)n * PFE_PFD_NDM * sizeof(float) + al) + ((size_t)n * 8 * sizeof(double) + al) +
          256;
@@ -338,15 +342,24 @@ static char* carve(char*& p, size_t bytes) {
   return r;
 }
 
+const double* pfd22_params(const void* work) {
+  char* p = (char*)work;
+  return (const double*)carve(p, 0);  // launch_pfd22 carves par22 first when no fit runs
+}
+
 // pa: the PFD inputs (profs, subfreqs, scal, shape, n); out n x 22, status n (device)
 hipError_t launch_pfd22(PfdArgs pa, double* out, uint32_t* status, void* work, size_t work_bytes,
-                        hipStream_t st, const Fork* fk, const Options& o) {
+                        hipStream_t st, const Fork* fk, const Options& o, unsigned groups,
+                        bool raw_dm) {
   const int64_t n = pa.n;
   const int L = pa.L;
-  if (work_bytes < pfd22_workspace_bytes(n, L)) return hipErrorInvalidValue;
+  if (work_bytes < pfd22_workspace_bytes(n, L, groups)) return hipErrorInvalidValue;
+  const bool all = groups == PFD_G_ALL, dm = (groups & PFD_G_DM) != 0;
   char* p = (char*)work;
-  double* profile = (double*)carve(p, (size_t)n * L * sizeof(double));
-  float* chis = (float*)carve(p, (size_t)n * PFE_PFD_NDM * sizeof(float));
+  // one group: no profile leaves the kernel (the fits on it are not run), and the sweep
+  // runs only for the DM fit (the kernels skip it when chis and lyon8 are null)
+  double* profile = all ? (double*)carve(p, (size_t)n * L * sizeof(double)) : nullptr;
+  float* chis = dm ? (float*)carve(p, (size_t)n * PFE_PFD_NDM * sizeof(float)) : nullptr;
   double* par22 = (double*)carve(p, (size_t)n * 8 * sizeof(double));
   char* bwork = carve(p, 0);
   hipError_t e = hipMemsetAsync(out, 0, (size_t)n * 22 * sizeof(double), st);
@@ -357,7 +370,12 @@ hipError_t launch_pfd22(PfdArgs pa, double* out, uint32_t* status, void* work, s
   pa.status = status;
   pa.out22 = out;
   pa.par22 = par22;
+  pa.groups = groups;
   if ((e = launch_pfd_dmprof(pa, st)) != hipSuccess) return e;
+  if (!dm) {
+    launch_clear_internal(status, n, st);
+    return hipGetLastError();
+  }
   BatesArgs a;
   bates_setup(a, n, L, bwork, o);
   a.prof = nullptr;
@@ -370,18 +388,20 @@ hipError_t launch_pfd22(PfdArgs pa, double* out, uint32_t* status, void* work, s
   a.scal = par22;
   a.out = out;
   a.status = status;
+  a.raw_dm = raw_dm ? 1 : 0;
   e = hipMemsetAsync(a.counters, 0, BATES_NCOUNTERS * sizeof(unsigned), st);
   if (e != hipSuccess) return e;
-  const bool forked = fork_begin(fk, st);
+  // the DM fit alone stays on the caller's stream
+  const bool forked = all && fork_begin(fk, st);
   const hipStream_t sg = forked ? fk->side[0] : st, sd = forked ? fk->side[1] : st;
-  if ((e = launch_gauss(a, sg)) != hipSuccess) return e;
+  if (all && (e = launch_gauss(a, sg)) != hipSuccess) return e;
   const PfdDMArgs d{a, chis};
   if (a.solver == PFE_SOLVER_POOLED)  // pooled group-LM unless the handle selects another solver
     hipLaunchKernelGGL((k_pfd_dmfitg<2>), dim3((unsigned)a.pwaves), dim3(64), 0, sd, d);
   else
     hipLaunchKernelGGL((k_pfd_dmfitb<2, BLM_FPW>), dim3((unsigned)((n + a.fpw - 1) / a.fpw)),
                        dim3(64), 0, sd, d);
-  if ((e = launch_sine(a, st)) != hipSuccess) return e;
+  if (all && (e = launch_sine(a, st)) != hipSuccess) return e;
   if (forked && (e = fork_end(fk, st)) != hipSuccess) return e;
   launch_clear_internal(status, n, st);
   return hipGetLastError();

@@ -611,7 +611,7 @@ __device__ __forceinline__ void pfd_finish(const PfdArgs& a, int64_t c, double* 
       }
     }
   }
-  uint32_t st = dm_ok ? 0u : PFE_ST_PFD_DMCURVE_FAIL;
+  uint32_t st = (dm_ok || !(a.groups & PFD_G_DM)) ? 0u : PFE_ST_PFD_DMCURVE_FAIL;
   if (a.out22) {
     double snr, width;
     pfd_params<NC>(buf, tmp, L, lane, snr, width);
@@ -619,9 +619,11 @@ __device__ __forceinline__ void pfd_finish(const PfdArgs& a, int64_t c, double* 
     const double span1 = dm_lo + ((dm_hi - dm_lo) * 1.0) / (double)(PFE_PFD_NDM - 1);
     const double span_last =
         dm_lo + ((dm_hi - dm_lo) * (double)(PFE_PFD_NDM - 1)) / (double)(PFE_PFD_NDM - 1);
-    double sb[3];
-    const bool sb_ok = pfd_subband_scores<NC>(T, buf, tmp, dl, sdb, bv, NS, L, lane, width, sb);
-    if (!sb_ok) st |= PFE_ST_SUBBAND_FAIL;
+    double sb[3] = {0.0, 0.0, 0.0};
+    // a.groups is a kernel argument: the branch is wave-uniform
+    if ((a.groups & PFD_G_SUB) &&
+        !pfd_subband_scores<NC>(T, buf, tmp, dl, sdb, bv, NS, L, lane, width, sb))
+      st |= PFE_ST_SUBBAND_FAIL;
     if (lane == 0) {
       double* o = a.out22 + c * 22;
       o[11] = period;                                                 // s12 (PFDFile.py:776)

@@ -8,22 +8,52 @@ Reference classes (PulsarFeatureExtractor/src/) and what replaces them here:
   PHCXOperations              PHCXOperations.py:44-             -> PHCXOperations
                               (getCandidateParameters :81-112, getDMFittings :121-233,
                                getSubbandParameters :305-349)
+  PFDOperations               PFDOperations.py:62-466           -> PFDOperations
+                              (getCandidateParameters :93-233, getDMCurveData :242-272,
+                               getDMFittings :274-393, getSubbandParameters :401-466)
 
 A reference-side subclass that needs one score group (PHCXFile.py:454, :521, :569, :613,
 :654 call one method each) binds the matching C-ABI function.  Every method here scores one
 candidate (the reference's granularity); the `*_batch` forms take n candidates at once.
 Values are the bits of the same group's columns of pfe_bates22 (same kernels); where the
 reference raises inside a method, the method raises ``Exception`` with the text PHCXFile
-reports for that group (candidate.GROUP_ERRORS).  Profiles are the PHCX byte profiles
-(integers 0-255); the PFD path's float profiles go through pfd.py / pfe_pfd_bates22.
+reports for that group (candidate.GROUP_ERRORS).  ProfileOperations and PHCXOperations take
+the PHCX byte profiles (integers 0-255); PFDOperations also takes the float 0..255 profile of
+a PFD (pfe_sinusoid4_f64 / pfe_gauss7_f64) and scores the fold's own groups through
+pfe_pfd_params4 / pfe_pfd_dmfit4 / pfe_pfd_subband3.
 """
 from __future__ import annotations
 
 import numpy as np
 
+import math
+
+from . import pfd as _pfd
 from . import phcx as _phcx
-from ._native import PFE_NSCAL, Engine
+from ._native import PFE_NSCAL, PFE_ST_PFD_DMCURVE_FAIL, Engine
 from .candidate import get_engine, status_error
+
+
+def _py2div(a, b):
+    """Python-2 '/': floor division when both operands are integers (the reference runs under
+    Python 2.7)."""
+    def integral(v):
+        return isinstance(v, (int, np.integer)) or (isinstance(v, np.ndarray) and v.dtype.kind in "iu")
+
+    return a // b if integral(a) and integral(b) else a / b
+
+
+def _score_at_percentile(data, per):
+    """scipy.stats.scoreatpercentile(data, per) with its default 'fraction' interpolation, in
+    scipy's own operations: the two neighbours of the fractional index weighted by their
+    distance to it."""
+    srt = np.sort(np.asarray(data))
+    idx = per / 100.0 * (srt.shape[0] - 1)
+    i = int(idx)
+    if i != idx:
+        w = np.array([(i + 1) - idx, idx - i], float)
+        return np.add.reduce(srt[i:i + 2] * w) / w.sum()
+    return np.add.reduce(srt[i:i + 1] * np.array(1)) / 1.0
 
 
 class ProfileOperationsInterface:
@@ -70,6 +100,27 @@ class ProfileOperationsInterface:
 
     def getSubbandParameters(self, data=None, profile=None):
         raise NotImplementedError("Please Implement this method")
+
+    # ---- the interface's concrete helpers (:138-207), on the host ------------------------
+    def freedmanDiaconisRule(self, data):
+        """:138-166 -- the number of histogram bins by the Freedman-Diaconis rule; a bin
+        width <= 0 (no interquartile range) falls back to 60."""
+        iqr = _score_at_percentile(data, 75) - _score_at_percentile(data, 25)
+        binwidth = 2 * iqr * pow(len(data), -0.3333333)
+        if binwidth <= 0:
+            binwidth = 60
+        rnge = max(data) - min(data)
+        return int(math.ceil(_py2div(rnge, binwidth)))
+
+    def getDerivative(self, yData):
+        """:170-186 -- dy[i] = y[i] - y[i+1], as a list."""
+        return [yData[i] - yData[i + 1] for i in range(len(yData) - 1)]
+
+    def scale(self, x, min_, max_, newMin, newMax):
+        """:190-207 -- x from [min_, max_] to [newMin, newMax], with the reference's Python-2
+        '/': all-integer arguments divide as integers."""
+        t = _py2div(x - min_, max_ - min_)
+        return (newMin * (1 - t)) + (newMax * t)
 
 
 def _u8_rows(profile) -> np.ndarray:
@@ -247,5 +298,102 @@ class PHCXOperations(ProfileOperations):
         c = self._cand(data, section)
         prof = c.profile if profile is None else profile
         out, st = self.getSubbandParameters_batch(prof, c.subbands[None], c.scal[None, :])
+        _raise_failed(st)
+        return [float(v) for v in out[0]]
+
+
+def _profile_rows(profile):
+    """Rows of a profile argument and whether they take the float path: byte-valued profiles
+    stay uint8 (the kernels PHCX files use), anything else goes as float64."""
+    try:
+        return _u8_rows(profile), False
+    except TypeError:
+        p = np.asarray(profile, dtype=np.float64)
+        return np.ascontiguousarray(p[None, :] if p.ndim == 1 else p), True
+
+
+class PFDOperations(ProfileOperations):
+    """PFDOperations.py:62-466: the groups of a PRESTO fold.  `data` is what the reference
+    passes -- the PFDFile object (candidate.PFDFile, or any object with the fold's attributes
+    as PFDFile.load sets them) -- or a fold read by pfd.read, or a .pfd path."""
+
+    @staticmethod
+    def _fold(data):
+        if isinstance(data, str):
+            return _pfd.read(data)
+        inner = getattr(data, "data", None)
+        return inner if isinstance(inner, _pfd.PFDData) else data
+
+    def _inputs(self, data):
+        return _pfd.batch_inputs([self._fold(data)])
+
+    # ---- batched forms -------------------------------------------------------------------
+    def getSinusoidFittings_batch(self, profiles):
+        p, f64 = _profile_rows(profiles)
+        return self.engine.sinusoid4_f64(p) if f64 else super().getSinusoidFittings_batch(p)
+
+    def getGaussianFittings_batch(self, profiles):
+        p, f64 = _profile_rows(profiles)
+        return self.engine.gauss7_f64(p) if f64 else super().getGaussianFittings_batch(p)
+
+    def getCandidateParameters_batch(self, profs, subfreqs, scal):
+        """Folds of one shape, as pfd.batch_inputs packs them -> ((n, 4), status)."""
+        return self.engine.pfd_params4(profs, subfreqs, scal)
+
+    def getDMFittings_batch(self, profs, subfreqs, scal):
+        return self.engine.pfd_dmfit4(profs, subfreqs, scal)
+
+    def getSubbandParameters_batch(self, profs, subfreqs, scal):
+        return self.engine.pfd_subband3(profs, subfreqs, scal)
+
+    # ---- per fold (the reference's signatures) -------------------------------------------
+    def getCandidateParameters(self, data):
+        """:93-233 -> [period (ms), snr, dm, width] as the method returns them (PFDFile applies
+        filterScore(13/14) when it stores s13/s14)."""
+        out, _st = self.getCandidateParameters_batch(*self._inputs(data))
+        return [float(v) for v in out[0]]
+
+    def _dm_curve(self, data):
+        r = self.engine.pfd_dmprof(*self._inputs(data), profile=False, lyon8=False)
+        if int(r["status"][0]) & PFE_ST_PFD_DMCURVE_FAIL:  # numdms == 1: dms[0] raises
+            raise Exception("DM curve extraction exception")
+        return r["chis"][0]
+
+    def getDMCurveData(self, data):
+        """:242-252 -- the float32 chi^2-vs-DM curve over span(dms[0], dms[-1], 100)."""
+        return self._dm_curve(data)
+
+    def getDMCurveDataNormalised(self, data):
+        """:254-272 -- 255./max(y)*y of that curve, in float32 as numpy evaluates it."""
+        y = self._dm_curve(data)
+        return np.float32(255.0) / max(y) * y
+
+    def getDMFittings(self, data):
+        """:274-393 -> (peak, |1 - Prop|, Shift, chi_theo) (s18 = filterScore(18, Shift))."""
+        out, st = self.getDMFittings_batch(*self._inputs(data))
+        _raise_failed(st)
+        return tuple(float(v) for v in out[0])
+
+    def getSubbandParameters(self, data=None, profile=None):
+        """:401-441 -> [RMS of peak positions, mean pair correlation, correlation integral];
+        [0.0, 0.0, 0.0] with neither argument (:425-426).
+
+        The boxcar width is the fold's own: the reference reads ``self.width``, which an
+        earlier getCandidateParameters call on the same fold left behind, and the kernel
+        derives the same width from the fold.  ``profile`` is accepted only when it is None
+        or equals the fold's own 0..255 profile (what PFDFile passes); the kernel correlates
+        the sub-bands with that profile, so any other raises ValueError."""
+        if data is None and profile is None:
+            return [0.0, 0.0, 0.0]
+        if data is None:
+            raise ValueError("getSubbandParameters: a profile without its fold")
+        ins = self._inputs(data)
+        if profile is not None:
+            own = self.engine.pfd_dmprof(*ins, chis=False, lyon8=False)["profile"][0]
+            given = np.asarray(profile, dtype=np.float64)
+            if given.shape != own.shape or not np.array_equal(given, own, equal_nan=True):
+                raise ValueError("getSubbandParameters: only the fold's own profile "
+                                 "(PFDFile.getProfile()) is supported")
+        out, st = self.getSubbandParameters_batch(*ins)
         _raise_failed(st)
         return [float(v) for v in out[0]]

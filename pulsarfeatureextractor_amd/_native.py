@@ -185,65 +185,38 @@ def load_library(path: str | None = None) -> C.CDLL:
             _preload_torch_hip_runtime()
         lib = C.CDLL(p)
         vp, i32, i64, u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32
-        lib.pfe_abi_version.restype = C.c_int
-        lib.pfe_abi_version.argtypes = []
-        lib.pfe_device_count.restype = C.c_int
-        lib.pfe_device_count.argtypes = []
-        lib.pfe_create.restype = C.c_int
-        lib.pfe_create.argtypes = [C.c_int, C.POINTER(vp)]
-        lib.pfe_destroy.restype = None
-        lib.pfe_destroy.argtypes = [vp]
-        lib.pfe_last_error.restype = C.c_char_p
-        lib.pfe_last_error.argtypes = [vp]
-        lib.pfe_set_stream.restype = C.c_int
-        lib.pfe_set_stream.argtypes = [vp, vp]
-        lib.pfe_synchronize.restype = C.c_int
-        lib.pfe_synchronize.argtypes = [vp]
-        lib.pfe_set_option.restype = C.c_int
-        lib.pfe_set_option.argtypes = [vp, i32, i64]
-        lib.pfe_get_option.restype = C.c_int
-        lib.pfe_get_option.argtypes = [vp, i32, C.POINTER(i64)]
-        lib.pfe_host_alloc.restype = C.c_int
-        lib.pfe_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
-        lib.pfe_host_free.restype = None
-        lib.pfe_host_free.argtypes = [vp]
-        lib.pfe_lyon8_u8.restype = C.c_int
-        lib.pfe_lyon8_u8.argtypes = [vp, vp, i64, i32, vp, i64, i32, i64, vp, vp, u32]
-        lib.pfe_lyon8_f64.restype = C.c_int
-        lib.pfe_lyon8_f64.argtypes = [vp, vp, i64, i32, vp, i64, i32, i64, vp, vp, u32]
-        lib.pfe_bates22.restype = C.c_int
-        lib.pfe_bates22.argtypes = [vp, C.POINTER(BatesIn), vp, vp, u32]
-        lib.pfe_subband3.restype = C.c_int
-        lib.pfe_subband3.argtypes = [vp, C.POINTER(BatesIn), vp, vp, u32]
-        for g in ("pfe_sinusoid4", "pfe_gauss7", "pfe_params4", "pfe_dmfit4"):
-            getattr(lib, g).restype = C.c_int
-            getattr(lib, g).argtypes = [vp, C.POINTER(BatesIn), vp, vp, u32]
-        lib.pfe_pfd_dmprof.restype = C.c_int
-        lib.pfe_pfd_dmprof.argtypes = [vp, C.POINTER(PfdIn), vp, vp, vp, vp, u32]
-        for g in ("pfe_pfd_bates22", "pfe_pfd_params4", "pfe_pfd_dmfit4", "pfe_pfd_subband3"):
-            getattr(lib, g).restype = C.c_int
-            getattr(lib, g).argtypes = [vp, C.POINTER(PfdIn), vp, vp, u32]
-        for g in ("pfe_sinusoid4_f64", "pfe_gauss7_f64"):
-            getattr(lib, g).restype = C.c_int
-            getattr(lib, g).argtypes = [vp, vp, i32, i64, vp, vp, u32]
-        pp = C.POINTER(C.c_char_p)
-        lib.pfe_phcx_parse.restype = C.c_int
-        lib.pfe_phcx_parse.argtypes = [pp, i64, i32, i32, C.POINTER(vp)]
-        lib.pfe_phcx_count.restype = i64
-        lib.pfe_phcx_count.argtypes = [vp]
-        lib.pfe_phcx_info_get.restype = C.c_int
-        lib.pfe_phcx_info_get.argtypes = [vp, i64, C.POINTER(PhcxInfo)]
-        lib.pfe_phcx_fetch.restype = C.c_int
-        lib.pfe_phcx_fetch.argtypes = [vp, i64, i32, vp, i64]
-        lib.pfe_phcx_pack.restype = C.c_int
-        lib.pfe_phcx_pack.argtypes = [vp, vp, i64, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp]
-        lib.pfe_phcx_free.restype = None
-        lib.pfe_phcx_free.argtypes = [vp]
-        lib.pfe_phcx_info_all.restype = C.c_int
-        lib.pfe_phcx_info_all.argtypes = [vp, vp, i64]
-        lib.pfe_format_rows.restype = C.c_int
-        lib.pfe_format_rows.argtypes = [vp, vp, vp, i64, i32, i64, i32, vp, i32, vp, i64,
-                                        C.POINTER(i64)]
+        ptr, rc = C.POINTER, C.c_int
+        lyon = [vp, vp, i64, i32, vp, i64, i32, i64, vp, vp, u32]
+        bates = [vp, ptr(BatesIn), vp, vp, u32]
+        pfd = [vp, ptr(PfdIn), vp, vp, u32]
+        f64 = [vp, vp, i32, i64, vp, vp, u32]
+        signatures = {  # name: (restype, argtypes), as include/pfe.h and include/pfe_io.h declare
+            "pfe_abi_version": (rc, []), "pfe_device_count": (rc, []),
+            "pfe_create": (rc, [C.c_int, ptr(vp)]), "pfe_destroy": (None, [vp]),
+            "pfe_last_error": (C.c_char_p, [vp]),
+            "pfe_set_stream": (rc, [vp, vp]), "pfe_synchronize": (rc, [vp]),
+            "pfe_set_option": (rc, [vp, i32, i64]), "pfe_get_option": (rc, [vp, i32, ptr(i64)]),
+            "pfe_host_alloc": (rc, [C.c_size_t, ptr(vp)]), "pfe_host_free": (None, [vp]),
+            "pfe_lyon8_u8": (rc, lyon), "pfe_lyon8_f64": (rc, lyon),
+            "pfe_bates22": (rc, bates), "pfe_subband3": (rc, bates),
+            "pfe_sinusoid4": (rc, bates), "pfe_gauss7": (rc, bates),
+            "pfe_params4": (rc, bates), "pfe_dmfit4": (rc, bates),
+            "pfe_sinusoid4_f64": (rc, f64), "pfe_gauss7_f64": (rc, f64),
+            "pfe_pfd_dmprof": (rc, [vp, ptr(PfdIn), vp, vp, vp, vp, u32]),
+            "pfe_pfd_bates22": (rc, pfd), "pfe_pfd_params4": (rc, pfd),
+            "pfe_pfd_dmfit4": (rc, pfd), "pfe_pfd_subband3": (rc, pfd),
+            "pfe_phcx_parse": (rc, [ptr(C.c_char_p), i64, i32, i32, ptr(vp)]),
+            "pfe_phcx_count": (i64, [vp]),
+            "pfe_phcx_info_get": (rc, [vp, i64, ptr(PhcxInfo)]),
+            "pfe_phcx_fetch": (rc, [vp, i64, i32, vp, i64]),
+            "pfe_phcx_pack": (rc, [vp, vp, i64, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp]),
+            "pfe_phcx_free": (None, [vp]), "pfe_phcx_info_all": (rc, [vp, vp, i64]),
+            "pfe_format_rows": (rc, [vp, vp, vp, i64, i32, i64, i32, vp, i32, vp, i64, ptr(i64)]),
+        }
+        assert set(signatures) == set(EXPORTED_SYMBOLS + EXPORTED_IO_SYMBOLS)
+        for name, (restype, argtypes) in signatures.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if path is None:
             _lib = lib
         return lib
@@ -427,6 +400,23 @@ class Engine:
             raise ValueError(f"out must be a contiguous ({n}, {width}) float64 array")
         return out
 
+    def _outputs(self, dev, like, n, k, out, status, need_status=True):
+        """Make or check `out` (n, k) and `status` (n,) where the inputs live (device: beside
+        the tensor `like`) -> (out, status, flags).  need_status False keeps a None status."""
+        if dev:
+            import torch
+
+            if out is None:
+                out = torch.empty((n, k), dtype=torch.float64, device=like.device)
+            self._dev(out, "out", (torch.float64,), (n, k))
+            if need_status or status is not None:
+                status = self._status_dev(status, n)
+            return out, status, PFE_FLAG_DEVICE_PTRS
+        out = self._out_host(out, n, k)
+        if need_status or status is not None:
+            status = self._status_host(status, n)
+        return out, status, 0
+
     # -- 8 Lyon features -----------------------------------------------------------------
     def lyon8(self, prof, dm, out=None, status=None):
         """[mean,std,skew,kurt] of each profile row then each DM row -> (n, 8) float64."""
@@ -443,13 +433,7 @@ class Engine:
             self._dev(dm, "dm", (prof.dtype,), rows_contig=True)
             kind = "u8" if prof.dtype == torch.uint8 else "f64"
             self._follow_torch()
-            if out is None:
-                out = torch.empty((n, 8), dtype=torch.float64, device=prof.device)
-            self._dev(out, "out", (torch.float64,), (n, 8))
-            if status is not None:
-                self._status_dev(status, n)
             ps, ds = _row_stride(prof.stride(0), prof), _row_stride(dm.stride(0), dm)
-            flags = PFE_FLAG_DEVICE_PTRS
         else:
             if prof.dtype == np.uint8 and dm.dtype == np.uint8:
                 kind = "u8"
@@ -461,10 +445,7 @@ class Engine:
             dm = dm if dm.strides[1] == dm.itemsize else np.ascontiguousarray(dm)
             ps = _row_stride(prof.strides[0] // prof.itemsize, prof)
             ds = _row_stride(dm.strides[0] // dm.itemsize, dm)
-            out = self._out_host(out, n, 8)
-            if status is not None:
-                self._status_host(status, n)
-            flags = 0
+        out, status, flags = self._outputs(dev, prof, n, 8, out, status, need_status=False)
         fn = self.lib.pfe_lyon8_u8 if kind == "u8" else self.lib.pfe_lyon8_f64
         st = None if status is None else _ptr(status)
         self._check(
@@ -508,19 +489,7 @@ class Engine:
     def bates22(self, prof, sub, dmcurve, scal, out=None, status=None):
         """22 scores per candidate -> ((n, 22) float64, (n,) status)."""
         bi, dev, keep = self._bates_args(prof, sub, dmcurve, scal, True)
-        n = bi.n
-        if dev:
-            import torch
-
-            if out is None:
-                out = torch.empty((n, 22), dtype=torch.float64, device=prof.device)
-            self._dev(out, "out", (torch.float64,), (n, 22))
-            status = self._status_dev(status, n)
-            flags = PFE_FLAG_DEVICE_PTRS
-        else:
-            out = self._out_host(out, n, 22)
-            status = self._status_host(status, n)
-            flags = 0
+        out, status, flags = self._outputs(dev, prof, bi.n, 22, out, status)
         self._check(self.lib.pfe_bates22(self._h, C.byref(bi), _ptr(out), _ptr(status), flags))
         del keep
         return out, status
@@ -529,19 +498,7 @@ class Engine:
         """Scores 20-22 alone (pfe_subband3, PHCXOperations.getSubbandParameters):
         -> ((n, 3) float64, (n,) status)."""
         bi, dev, keep = self._bates_args(prof, sub, None, scal, False)
-        n = bi.n
-        if dev:
-            import torch
-
-            if out is None:
-                out = torch.empty((n, 3), dtype=torch.float64, device=prof.device)
-            self._dev(out, "out", (torch.float64,), (n, 3))
-            status = self._status_dev(status, n)
-            flags = PFE_FLAG_DEVICE_PTRS
-        else:
-            out = self._out_host(out, n, 3)
-            status = self._status_host(status, n)
-            flags = 0
+        out, status, flags = self._outputs(dev, prof, bi.n, 3, out, status)
         self._check(self.lib.pfe_subband3(self._h, C.byref(bi), _ptr(out), _ptr(status), flags))
         del keep
         return out, status
@@ -558,18 +515,11 @@ class Engine:
                     self._dev(a, nm, (torch.uint8,) if nm == "prof" else (torch.float64,))
             self._dev(scal, "scal", (torch.float64,))
             self._follow_torch()
-            if out is None:
-                out = torch.empty((n, k), dtype=torch.float64, device=scal.device)
-            self._dev(out, "out", (torch.float64,), (n, k))
-            status = self._status_dev(status, n)
-            flags = PFE_FLAG_DEVICE_PTRS
         else:
             prof = None if prof is None else np.ascontiguousarray(prof, dtype=np.uint8)
             dmcurve = None if dmcurve is None else np.ascontiguousarray(dmcurve, dtype=np.float64)
             scal = np.ascontiguousarray(scal, dtype=np.float64)
-            out = self._out_host(out, n, k)
-            status = self._status_host(status, n)
-            flags = 0
+        out, status, flags = self._outputs(dev, scal, n, k, out, status)
         for a in (prof, dmcurve):
             if a is not None and a.shape[0] != n:
                 raise ValueError("inputs must have the same number of rows")
@@ -599,24 +549,18 @@ class Engine:
         if prof.ndim != 2:
             raise ValueError("prof must be (n, lp)")
         n, lp = prof.shape
-        if _is_device(prof):
+        dev = _is_device(prof)
+        if dev:
             import torch
 
             self._dev(prof, "prof", (torch.float64,))
             self._follow_torch()
-            if out is None:
-                out = torch.empty((n, k), dtype=torch.float64, device=prof.device)
-            self._dev(out, "out", (torch.float64,), (n, k))
-            status = self._status_dev(status, n)
-            flags = PFE_FLAG_DEVICE_PTRS
         else:
             if not isinstance(prof, np.ndarray) or prof.dtype != np.float64:
                 raise TypeError(f"{fn}: float64 profile rows expected (byte profiles go through "
                                 "sinusoid4 / gauss7)")
             prof = np.ascontiguousarray(prof)
-            out = self._out_host(out, n, k)
-            status = self._status_host(status, n)
-            flags = 0
+        out, status, flags = self._outputs(dev, prof, n, k, out, status)
         self._check(getattr(self.lib, fn)(self._h, _ptr(prof), lp, n, _ptr(out), _ptr(status),
                                           flags))
         return out, status
@@ -704,19 +648,7 @@ class Engine:
 
     def _pfd_scores(self, fn, k, profs, subfreqs, scal, out, status):
         pin, dev, keep = self._pfd_args(profs, subfreqs, scal, fn)
-        n = pin.n
-        if dev:
-            import torch
-
-            if out is None:
-                out = torch.empty((n, k), dtype=torch.float64, device=profs.device)
-            self._dev(out, "out", (torch.float64,), (n, k))
-            status = self._status_dev(status, n)
-            flags = PFE_FLAG_DEVICE_PTRS
-        else:
-            out = self._out_host(out, n, k)
-            status = self._status_host(status, n)
-            flags = 0
+        out, status, flags = self._outputs(dev, profs, pin.n, k, out, status)
         self._check(getattr(self.lib, "pfe_" + fn)(self._h, C.byref(pin), _ptr(out), _ptr(status),
                                                    flags))
         del keep

@@ -15,29 +15,8 @@
 #include <string>
 
 #include "../../include/pfe.h"
-#include "bates_common.h"
+#include "launch.h"
 #include "options.h"
-#include "pfd.h"
-
-namespace pfe {
-hipError_t launch_lyon8_u8(const uint8_t* prof, int64_t ps, int lp, const uint8_t* dm,
-                           int64_t ds, int ld, int64_t n, double* out, hipStream_t st,
-                           const Options& o);
-hipError_t launch_lyon8_f64(const double* prof, int64_t ps, int lp, const double* dm,
-                            int64_t ds, int ld, int64_t n, double* out, hipStream_t st,
-                            const Options& o);
-hipError_t launch_bates22(const pfe_bates_in* in, double* out, uint32_t* status, void* work,
-                          size_t work_bytes, hipStream_t st, const Fork* fk, const Options& o);
-size_t bates22_workspace_bytes(const pfe_bates_in* in);
-hipError_t launch_bates_groups(const pfe_bates_in* in, double* out, uint32_t* status, void* work,
-                               size_t work_bytes, hipStream_t st, const Fork* fk,
-                               const Options& o, unsigned groups, bool raw_dm,
-                               const double* fprof);
-hipError_t launch_subband3(const pfe_bates_in* in, double* out, uint32_t* status, void* work,
-                           hipStream_t st);
-const char* subband_shape_error(int nsub, int lsb);
-size_t subband_work_bytes(int64_t n, int nsub, int lsb);
-}  // namespace pfe
 
 // chunked host path: device/staging slots in flight (H2D of k+1 | kernel k | D2H of k-1)
 constexpr int PIPE_SLOTS = 3;
@@ -126,6 +105,56 @@ static int ensure_scratch(pfe_handle* h, size_t bytes) {
   PFE_HIP(h, hipMalloc(&h->scratch, want));
   h->scratch_bytes_peak = want;
   h->scratch_bytes = want;
+  // the one alignment every layout (arena.h) relies on
+  if ((uintptr_t)h->scratch & 255)
+    return set_err(h, PFE_EDEVICE, "hipMalloc: block not 256-byte aligned");
+  return PFE_OK;
+}
+
+// A call's scratch: the walk (a layout of launch.h) measures, the scratch grows to that,
+// and the same walk places the pointers -- only then, because growing moves the scratch
+template <class S, class F>
+static int lay_out(pfe_handle* h, S& s, F walk) {
+  pfe::Arena measure;
+  walk(measure);
+  int rc = ensure_scratch(h, measure.bytes());
+  if (rc) return rc;
+  pfe::Arena place{(uintptr_t)h->scratch};
+  s = walk(place);
+  return PFE_OK;
+}
+
+// The checks every call on a batch starts with: PFE_OK and n > 0 when there is work to do.
+// args: the caller's pointer arguments besides `in` are all there
+template <class In>
+static int call_check(pfe_handle* h, const char* fn, const In* in, bool args, int64_t& n) {
+  n = 0;
+  if (!h) return PFE_EINVAL;
+  h->err.clear();
+  if (!in || !args) return set_err(h, PFE_EINVAL, "%s: null argument", fn);
+  if (in->n < 0) return set_err(h, PFE_EINVAL, "%s: n < 0", fn);
+  n = in->n;
+  return PFE_OK;
+}
+
+// host -> a region the layout took, on the call's stream
+template <class T>
+static int stage_in(pfe_handle* h, T* dst, const void* src, size_t count) {
+  PFE_HIP(h, hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
+  return PFE_OK;
+}
+template <class T>
+static int fetch(pfe_handle* h, T* dst, const T* src, size_t count) {
+  PFE_HIP(h, hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+  return PFE_OK;
+}
+// the end of a host-pointer call: out (n x k, or null), status, and the results are there
+static int fetch_out(pfe_handle* h, double* out, const double* dout, int k, uint32_t* status,
+                     const uint32_t* dstat, int64_t n) {
+  int rc = out ? fetch(h, out, dout, (size_t)n * k) : PFE_OK;
+  if (!rc) rc = fetch(h, status, dstat, (size_t)n);
+  if (rc) return rc;
+  PFE_HIP(h, hipStreamSynchronize(h->stream));
   return PFE_OK;
 }
 
@@ -140,8 +169,6 @@ static int ensure_pinned(pfe_handle* h, size_t bytes) {
   h->pin_bytes = bytes;
   return PFE_OK;
 }
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // host memory the DMA engines can read directly (hipHostMalloc / hipHostRegister)
 static bool is_pinned(const void* p) {
@@ -373,10 +400,14 @@ static int lyon8_host(pfe_handle* h, const T* prof, int64_t ps, int32_t lp, cons
   int64_t chunk = (int64_t)(PIPE_CHUNK_BYTES / row_in);
   chunk = std::max<int64_t>(1024, chunk & ~(int64_t)63);
   if (chunk > n) chunk = n;
-  const size_t pb = align256((size_t)chunk * lp * sizeof(T));
-  const size_t db = align256((size_t)chunk * ld * sizeof(T));
-  const size_t ob = align256((size_t)chunk * 8 * sizeof(double));
-  const size_t slot = pb + db + ob;
+  // every slot has one layout, in the device scratch and in the pinned staging ring
+  pfe::Arena one;
+  pfe::lyon8_slot_layout<T>(one, chunk, lp, ld);
+  const size_t slot = one.bytes();
+  auto slot_at = [&](void* ring, int s) {
+    pfe::Arena a{(uintptr_t)ring, s * slot};
+    return pfe::lyon8_slot_layout<T>(a, chunk, lp, ld);
+  };
   int rc = ensure_scratch(h, PIPE_SLOTS * slot);
   if (rc) return rc;
   const bool pin_p = is_pinned(prof), pin_d = is_pinned(dm), pin_o = is_pinned(out);
@@ -403,25 +434,23 @@ static int lyon8_host(pfe_handle* h, const T* prof, int64_t ps, int32_t lp, cons
     const int s = (int)(k % PIPE_SLOTS);
     PFE_HIP(h, hipEventSynchronize(h->ev_out[s]));
     if (!pin_o)
-      memcpy(out + k * chunk * 8, (char*)h->pin + s * slot + pb + db,
-             (size_t)rows_of(k) * 8 * sizeof(double));
+      memcpy(out + k * chunk * 8, slot_at(h->pin, s).out, (size_t)rows_of(k) * 8 * sizeof(double));
     return PFE_OK;
   };
   for (int64_t k = 0; k < K; ++k) {
     const int s = (int)(k % PIPE_SLOTS);
     const int64_t r0 = k * chunk, rows = rows_of(k);
-    char* dslot = (char*)h->scratch + s * slot;
-    char* hslot = h->pin ? (char*)h->pin + s * slot : nullptr;
-    T* dprof = (T*)dslot;
-    T* ddm = (T*)(dslot + pb);
-    double* dout = (double*)(dslot + pb + db);
+    const pfe::Lyon8Slot<T> d = slot_at(h->scratch, s);
+    const pfe::Lyon8Slot<T> hs = slot_at(h->pin, s);  // staging of a caller's pageable arrays
+    T *dprof = d.prof, *ddm = d.dm;
+    double* dout = d.out;
     if (k >= PIPE_SLOTS) {
       // slot reuse: chunk k-3's staged output is drained (and with it its H2D and kernel)
       rc = unstage_out(k - PIPE_SLOTS);
       if (rc) return rc;
     }
-    if (!pin_p) pack_rows((T*)hslot, prof, ps, lp, r0, rows);
-    if (!pin_d) pack_rows((T*)(hslot + pb), dm, ds, ld, r0, rows);
+    if (!pin_p) pack_rows(hs.prof, prof, ps, lp, r0, rows);
+    if (!pin_d) pack_rows(hs.dm, dm, ds, ld, r0, rows);
     if (pin_p && ps == lp)
       PFE_HIP(h, hipMemcpyAsync(dprof, prof + r0 * ps, (size_t)rows * lp * sizeof(T),
                                 hipMemcpyHostToDevice, h->h2d));
@@ -429,7 +458,7 @@ static int lyon8_host(pfe_handle* h, const T* prof, int64_t ps, int32_t lp, cons
       PFE_HIP(h, hipMemcpy2DAsync(dprof, lp * sizeof(T), prof + r0 * ps, ps * sizeof(T),
                                   lp * sizeof(T), rows, hipMemcpyHostToDevice, h->h2d));
     else
-      PFE_HIP(h, hipMemcpyAsync(dprof, hslot, (size_t)rows * lp * sizeof(T),
+      PFE_HIP(h, hipMemcpyAsync(dprof, hs.prof, (size_t)rows * lp * sizeof(T),
                                 hipMemcpyHostToDevice, h->h2d));
     if (pin_d && ds == ld)
       PFE_HIP(h, hipMemcpyAsync(ddm, dm + r0 * ds, (size_t)rows * ld * sizeof(T),
@@ -438,7 +467,7 @@ static int lyon8_host(pfe_handle* h, const T* prof, int64_t ps, int32_t lp, cons
       PFE_HIP(h, hipMemcpy2DAsync(ddm, ld * sizeof(T), dm + r0 * ds, ds * sizeof(T),
                                   ld * sizeof(T), rows, hipMemcpyHostToDevice, h->h2d));
     else
-      PFE_HIP(h, hipMemcpyAsync(ddm, hslot + pb, (size_t)rows * ld * sizeof(T),
+      PFE_HIP(h, hipMemcpyAsync(ddm, hs.dm, (size_t)rows * ld * sizeof(T),
                                 hipMemcpyHostToDevice, h->h2d));
     PFE_HIP(h, hipEventRecord(h->ev_in[s], h->h2d));
     PFE_HIP(h, hipStreamWaitEvent(h->stream, h->ev_in[s], 0));
@@ -446,7 +475,7 @@ static int lyon8_host(pfe_handle* h, const T* prof, int64_t ps, int32_t lp, cons
     if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "lyon8 launch: %s", hipGetErrorString(e));
     PFE_HIP(h, hipEventRecord(h->ev_k[s], h->stream));
     PFE_HIP(h, hipStreamWaitEvent(h->d2h, h->ev_k[s], 0));
-    PFE_HIP(h, hipMemcpyAsync(pin_o ? (void*)(out + r0 * 8) : (void*)(hslot + pb + db), dout,
+    PFE_HIP(h, hipMemcpyAsync(pin_o ? out + r0 * 8 : hs.out, dout,
                               (size_t)rows * 8 * sizeof(double), hipMemcpyDeviceToHost, h->d2h));
     PFE_HIP(h, hipEventRecord(h->ev_out[s], h->d2h));
   }
@@ -528,115 +557,55 @@ static int check_bates_in(pfe_handle* h, const pfe_bates_in* in, const char* fn,
   return PFE_OK;
 }
 
-// one-shot staging of a host-pointer batch: inputs -> scratch, then `nout` doubles and a
-// status word per row of output space
-static int stage_bates(pfe_handle* h, const pfe_bates_in* in, pfe_bates_in& din, int nout,
-                       bool with_dm, size_t work, double*& dout, uint32_t*& dstat, size_t& off) {
-  const int64_t n = in->n;
-  hipStream_t st = h->stream;
-  const size_t pb = align256((size_t)n * in->lp);
-  const size_t sb = align256((size_t)n * in->nsub * in->lsb);
-  const size_t db = with_dm ? align256((size_t)n * in->ndm * sizeof(double)) : 0;
-  const size_t cb = align256((size_t)n * PFE_NSCAL * sizeof(double));
-  const size_t ob = align256((size_t)n * nout * sizeof(double));
-  const size_t tb = align256((size_t)n * sizeof(uint32_t));
-  int rc = ensure_scratch(h, pb + sb + db + cb + ob + tb + work);
+// pfe_bates22 (chain: the 22 scores) and pfe_subband3: on the host path the inputs go to the
+// scratch and the results come back; the launcher works behind them
+static int score_call(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* status,
+                      uint32_t flags, const char* fn, bool chain) {
+  int64_t n;
+  int rc = call_check(h, fn, in, out && status, n);
+  if (rc || n == 0) return rc;
+  if ((rc = check_bates_in(h, in, fn, chain)) || (rc = call_begin(h))) return rc;
+  const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
+  const size_t sub_bytes = pfe::subband_work_bytes(n, in->nsub, in->lsb);
+  const int cus = chain ? pfe::device_cus() : 0;
+  pfe::ScoreStage s;
+  rc = lay_out(h, s, [&](pfe::Arena& A) {
+    return pfe::score_layout(A, *in, host, chain, sub_bytes, cus, h->opt);
+  });
   if (rc) return rc;
-  char* base = (char*)h->scratch;
-  PFE_HIP(h, hipMemcpyAsync(base, in->prof, (size_t)n * in->lp, hipMemcpyHostToDevice, st));
-  din.prof = (const uint8_t*)base;
-  off = pb;
-  PFE_HIP(h, hipMemcpyAsync(base + off, in->sub, (size_t)n * in->nsub * in->lsb,
-                            hipMemcpyHostToDevice, st));
-  din.sub = (const uint8_t*)(base + off);
-  off += sb;
-  if (with_dm) {
-    PFE_HIP(h, hipMemcpyAsync(base + off, in->dmcurve, (size_t)n * in->ndm * sizeof(double),
-                              hipMemcpyHostToDevice, st));
-    din.dmcurve = (const double*)(base + off);
-    off += db;
+  pfe_bates_in din = *in;
+  if (host) {
+    const size_t m = (size_t)n;
+    if ((rc = stage_in(h, s.prof, in->prof, m * in->lp)) ||
+        (rc = stage_in(h, s.sub, in->sub, m * in->nsub * in->lsb)) ||
+        (chain && (rc = stage_in(h, s.dmcurve, in->dmcurve, m * in->ndm))) ||
+        (rc = stage_in(h, s.scal, in->scal, m * PFE_NSCAL)))
+      return rc;
+    din.prof = s.prof;
+    din.sub = s.sub;
+    if (chain) din.dmcurve = s.dmcurve;
+    din.scal = s.scal;
   }
-  PFE_HIP(h, hipMemcpyAsync(base + off, in->scal, (size_t)n * PFE_NSCAL * sizeof(double),
-                            hipMemcpyHostToDevice, st));
-  din.scal = (const double*)(base + off);
-  off += cb;
-  dout = (double*)(base + off);
-  off += ob;
-  dstat = (uint32_t*)(base + off);
-  off += tb;
-  return PFE_OK;
+  double* dout = host ? s.out : out;
+  uint32_t* dstat = host ? s.status : status;
+  hipStream_t st = h->stream;
+  hipError_t e = chain ? pfe::launch_bates22(&din, dout, dstat, s.bates, st, &h->fork, h->opt)
+                       : pfe::launch_subband3(&din, dout, dstat, s.sub_work, st);
+  if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
+  if (host && (rc = fetch_out(h, out, dout, chain ? 22 : 3, status, dstat, n))) return rc;
+  return call_end(h);
 }
 
 extern "C" {
 
 int pfe_bates22(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* status,
                 uint32_t flags) {
-  if (!h) return PFE_EINVAL;
-  h->err.clear();
-  if (!in || !out || !status) return set_err(h, PFE_EINVAL, "bates22: null argument");
-  const int64_t n = in->n;
-  if (n < 0) return set_err(h, PFE_EINVAL, "bates22: n < 0");
-  if (n == 0) return PFE_OK;
-  int rc = check_bates_in(h, in, "bates22", true);
-  if (rc) return rc;
-  rc = call_begin(h);
-  if (rc) return rc;
-  hipStream_t st = h->stream;
-  pfe_bates_in din = *in;
-  double* dout = out;
-  uint32_t* dstat = status;
-  size_t off = 0;
-  const size_t work = pfe::bates22_workspace_bytes(in);
-  if (!(flags & PFE_FLAG_DEVICE_PTRS)) {
-    rc = stage_bates(h, in, din, 22, true, work, dout, dstat, off);
-  } else {
-    rc = ensure_scratch(h, work);
-  }
-  if (rc) return rc;
-  hipError_t e = pfe::launch_bates22(&din, dout, dstat, (char*)h->scratch + off, work, st,
-                                     &h->fork, h->opt);
-  if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "bates22 launch: %s", hipGetErrorString(e));
-  if (!(flags & PFE_FLAG_DEVICE_PTRS)) {
-    PFE_HIP(h, hipMemcpyAsync(out, dout, (size_t)n * 22 * sizeof(double), hipMemcpyDeviceToHost, st));
-    PFE_HIP(h, hipMemcpyAsync(status, dstat, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    PFE_HIP(h, hipStreamSynchronize(st));
-  }
-  return call_end(h);
+  return score_call(h, in, out, status, flags, "bates22", true);
 }
 
 int pfe_subband3(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* status,
                  uint32_t flags) {
-  if (!h) return PFE_EINVAL;
-  h->err.clear();
-  if (!in || !out || !status) return set_err(h, PFE_EINVAL, "subband3: null argument");
-  const int64_t n = in->n;
-  if (n < 0) return set_err(h, PFE_EINVAL, "subband3: n < 0");
-  if (n == 0) return PFE_OK;
-  int rc = check_bates_in(h, in, "subband3", false);
-  if (rc) return rc;
-  rc = call_begin(h);
-  if (rc) return rc;
-  hipStream_t st = h->stream;
-  pfe_bates_in din = *in;
-  double* dout = out;
-  uint32_t* dstat = status;
-  size_t off = 0;
-  const size_t work = pfe::subband_work_bytes(n, in->nsub, in->lsb);
-  if (!(flags & PFE_FLAG_DEVICE_PTRS)) {
-    rc = stage_bates(h, in, din, 3, false, work ? work + 256 : 0, dout, dstat, off);
-  } else if (work) {
-    rc = ensure_scratch(h, work + 256);
-  }
-  if (rc) return rc;
-  void* wp = work ? (void*)(((uintptr_t)h->scratch + off + 255) & ~(uintptr_t)255) : nullptr;
-  hipError_t e = pfe::launch_subband3(&din, dout, dstat, wp, st);
-  if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "subband3 launch: %s", hipGetErrorString(e));
-  if (!(flags & PFE_FLAG_DEVICE_PTRS)) {
-    PFE_HIP(h, hipMemcpyAsync(out, dout, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    PFE_HIP(h, hipMemcpyAsync(status, dstat, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    PFE_HIP(h, hipStreamSynchronize(st));
-  }
-  return call_end(h);
+  return score_call(h, in, out, status, flags, "subband3", false);
 }
 
 }  // extern "C"
@@ -667,12 +636,9 @@ __global__ void k_params4(const double* scal, int64_t n, double* out, uint32_t* 
 static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* status,
                             uint32_t flags, const char* fn, unsigned groups, int c0, int k,
                             bool f64 = false, const double* fprof = nullptr) {
-  if (!h) return PFE_EINVAL;
-  h->err.clear();
-  if (!in || !out || !status) return set_err(h, PFE_EINVAL, "%s: null argument", fn);
-  const int64_t n = in->n;
-  if (n < 0) return set_err(h, PFE_EINVAL, "%s: n < 0", fn);
-  if (n == 0) return PFE_OK;
+  int64_t n;
+  int rc = call_check(h, fn, in, out && status, n);
+  if (rc || n == 0) return rc;
   const bool dm = groups == pfe::BG_DM;
   if (f64 ? !fprof : (!in->scal || (dm ? !in->dmcurve : !in->prof)))
     return set_err(h, PFE_EINVAL, "%s: null input array", fn);
@@ -680,8 +646,7 @@ static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, 
     return set_err(h, PFE_EINVAL, "%s: lp=%d outside [8,1024]", fn, in->lp);
   if (dm && (in->ndm < 3 || in->ndm > 1024))
     return set_err(h, PFE_EINVAL, "%s: ndm=%d outside [3,1024]", fn, in->ndm);
-  int rc = call_begin(h);
-  if (rc) return rc;
+  if ((rc = call_begin(h))) return rc;
   hipStream_t st = h->stream;
   // only the arrays the group reads; no sub-band work
   pfe_bates_in g = *in;
@@ -696,56 +661,39 @@ static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, 
     g.ndm = 0;
   }
   const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
-  const size_t work = pfe::bates22_workspace_bytes(&g);
-  const size_t psz = f64 ? sizeof(double) : 1;  // bytes per profile bin
-  const size_t pb = host && !dm ? align256((size_t)n * g.lp * psz) : 0;
-  const size_t db = host && dm ? align256((size_t)n * g.ndm * sizeof(double)) : 0;
-  const size_t cb = host && !f64 ? align256((size_t)n * PFE_NSCAL * sizeof(double)) : 0;
-  const size_t ob = align256((size_t)n * 22 * sizeof(double));
-  const size_t kb = host ? align256((size_t)n * k * sizeof(double)) : 0;
-  const size_t tb = host ? align256((size_t)n * sizeof(uint32_t)) : 0;
-  rc = ensure_scratch(h, pb + db + cb + ob + kb + tb + work + 256);
+  const int cus = pfe::device_cus();
+  pfe::GroupStage s;
+  rc = lay_out(h, s, [&](pfe::Arena& A) {
+    return pfe::group_layout(A, n, g.lp, g.ndm, groups, f64, k, host, cus, h->opt);
+  });
   if (rc) return rc;
-  char* base = (char*)(((uintptr_t)h->scratch + 255) & ~(uintptr_t)255);
-  pfe_bates_in din = g;
-  size_t off = 0;
   if (host) {
+    const size_t m = (size_t)n;
     if (dm) {
-      PFE_HIP(h, hipMemcpyAsync(base, in->dmcurve, (size_t)n * g.ndm * sizeof(double),
-                                hipMemcpyHostToDevice, st));
-      din.dmcurve = (const double*)base;
+      rc = stage_in(h, s.dmcurve, in->dmcurve, m * g.ndm);
+      g.dmcurve = s.dmcurve;
     } else if (f64) {
-      PFE_HIP(h, hipMemcpyAsync(base, fprof, (size_t)n * g.lp * psz, hipMemcpyHostToDevice, st));
-      fprof = (const double*)base;
+      rc = stage_in(h, s.fprof, fprof, m * g.lp);
+      fprof = s.fprof;
     } else {
-      PFE_HIP(h, hipMemcpyAsync(base, in->prof, (size_t)n * g.lp, hipMemcpyHostToDevice, st));
-      din.prof = (const uint8_t*)base;
+      rc = stage_in(h, s.prof, in->prof, m * g.lp);
+      g.prof = s.prof;
     }
-    off = pb + db;
-    if (!f64) {
-      PFE_HIP(h, hipMemcpyAsync(base + off, in->scal, (size_t)n * PFE_NSCAL * sizeof(double),
-                                hipMemcpyHostToDevice, st));
-      din.scal = (const double*)(base + off);
+    if (!rc && !f64) {
+      rc = stage_in(h, s.scal, in->scal, m * PFE_NSCAL);
+      g.scal = s.scal;
     }
-    off += cb;
+    if (rc) return rc;
   }
-  double* d22 = (double*)(base + off);
-  off += ob;
-  double* dk = host ? (double*)(base + off) : out;
-  off += kb;
-  uint32_t* dst = host ? (uint32_t*)(base + off) : status;
-  off += tb;
-  hipError_t e = pfe::launch_bates_groups(&din, d22, dst, base + off, work, st, &h->fork, h->opt,
-                                          groups, dm, f64 ? fprof : nullptr);
+  double* dk = host ? s.out : out;
+  uint32_t* dst = host ? s.status : status;
+  hipError_t e = pfe::launch_bates_groups(&g, s.d22, dst, s.bates, st, &h->fork, h->opt, groups, dm,
+                                          f64 ? fprof : nullptr);
   if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
-  hipLaunchKernelGGL(k_take_cols, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st, d22,
+  hipLaunchKernelGGL(k_take_cols, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st, s.d22,
                      22, c0, k, n, dk);
   PFE_HIP(h, hipGetLastError());
-  if (host) {
-    PFE_HIP(h, hipMemcpyAsync(out, dk, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, st));
-    PFE_HIP(h, hipMemcpyAsync(status, dst, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    PFE_HIP(h, hipStreamSynchronize(st));
-  }
+  if (host && (rc = fetch_out(h, out, dk, k, status, dst, n))) return rc;
   return call_end(h);
 }
 
@@ -790,36 +738,22 @@ int pfe_gauss7_f64(pfe_handle* h, const double* prof, int32_t lp, int64_t n, dou
 
 int pfe_params4(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* status,
                 uint32_t flags) {
-  if (!h) return PFE_EINVAL;
-  h->err.clear();
-  if (!in || !out || !status || (in->n > 0 && !in->scal))
-    return set_err(h, PFE_EINVAL, "params4: null argument");
-  const int64_t n = in->n;
-  if (n < 0) return set_err(h, PFE_EINVAL, "params4: n < 0");
-  if (n == 0) return PFE_OK;
-  int rc = call_begin(h);
-  if (rc) return rc;
-  hipStream_t st = h->stream;
-  if (flags & PFE_FLAG_DEVICE_PTRS) {
-    hipLaunchKernelGGL(k_params4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in->scal,
-                       n, out, status);
-    PFE_HIP(h, hipGetLastError());
-    return call_end(h);
-  }
-  const size_t cb = align256((size_t)n * PFE_NSCAL * sizeof(double));
-  const size_t ob = align256((size_t)n * 4 * sizeof(double));
-  rc = ensure_scratch(h, cb + ob + (size_t)n * sizeof(uint32_t));
-  if (rc) return rc;
-  char* base = (char*)h->scratch;
-  PFE_HIP(h, hipMemcpyAsync(base, in->scal, (size_t)n * PFE_NSCAL * sizeof(double),
-                            hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_params4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                     (const double*)base, n, (double*)(base + cb), (uint32_t*)(base + cb + ob));
+  int64_t n;
+  int rc = call_check(h, "params4", in, out && status && !(in && in->n > 0 && !in->scal), n);
+  if (rc || n == 0) return rc;
+  if ((rc = call_begin(h))) return rc;
+  const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
+  pfe::GroupStage s;  // the host path's scal, out and status: no fit, no workspace
+  rc = lay_out(h, s, [&](pfe::Arena& A) {
+    return pfe::group_layout(A, n, 0, 0, 0, false, 4, host, 0, h->opt);
+  });
+  if (rc || (host && (rc = stage_in(h, s.scal, in->scal, (size_t)n * PFE_NSCAL)))) return rc;
+  double* dout = host ? s.out : out;
+  uint32_t* dstat = host ? s.status : status;
+  hipLaunchKernelGGL(k_params4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
+                     host ? s.scal : in->scal, n, dout, dstat);
   PFE_HIP(h, hipGetLastError());
-  PFE_HIP(h, hipMemcpyAsync(out, base + cb, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-  PFE_HIP(h, hipMemcpyAsync(status, base + cb + ob, (size_t)n * sizeof(uint32_t),
-                            hipMemcpyDeviceToHost, st));
-  PFE_HIP(h, hipStreamSynchronize(st));
+  if (host && (rc = fetch_out(h, out, dout, 4, status, dstat, n))) return rc;
   return call_end(h);
 }
 
@@ -836,14 +770,39 @@ static int pfd_shape_err(pfe_handle* h, const char* fn, const pfe_pfd_in* in) {
                  "(6*proflen + 3.5*nsub doubles = %zu bytes) <= %zu bytes of LDS",
                  fn, in->nsub, in->proflen, pfe::PFD_G_MAX_L, p.lds, pfe::PFD_LDS_LIMIT);
 }
+// the shape and the caller's arrays of a PFD call
+static pfe::PfdArgs pfd_args(const pfe_handle* h, const pfe_pfd_in* in) {
+  pfe::PfdArgs a;
+  a.profs = in->profs;
+  a.subfreqs = in->subfreqs;
+  a.scal = in->scal;
+  a.npart = in->npart;
+  a.nsub = in->nsub;
+  a.L = in->proflen;
+  a.n = in->n;
+  a.waves = h->opt.pfd_waves;
+  return a;
+}
+// host path: the three inputs into their regions `d`, and `a` reads them there
+static int stage_pfd(pfe_handle* h, const pfe_pfd_in* in, const pfe::PfdInputs& d,
+                     pfe::PfdArgs& a) {
+  const size_t n = (size_t)in->n;
+  int rc;
+  if ((rc = stage_in(h, d.profs, in->profs, n * in->npart * in->nsub * in->proflen)) ||
+      (rc = stage_in(h, d.subfreqs, in->subfreqs, n * in->nsub)) ||
+      (rc = stage_in(h, d.scal, in->scal, n * PFE_PFD_NSCAL)))
+    return rc;
+  a.profs = d.profs;
+  a.subfreqs = d.subfreqs;
+  a.scal = d.scal;
+  return PFE_OK;
+}
+
 int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* chis,
                    double* lyon8, uint32_t* status, uint32_t flags) {
-  if (!h) return PFE_EINVAL;
-  h->err.clear();
-  if (!in || !status) return set_err(h, PFE_EINVAL, "pfd_dmprof: null argument");
-  const int64_t n = in->n;
-  if (n < 0) return set_err(h, PFE_EINVAL, "pfd_dmprof: n < 0");
-  if (n == 0) return PFE_OK;
+  int64_t n;
+  int rc = call_check(h, "pfd_dmprof", in, status != nullptr, n);
+  if (rc || n == 0) return rc;
   if (!in->profs || !in->subfreqs || !in->scal)
     return set_err(h, PFE_EINVAL, "pfd_dmprof: null input array");
   if (in->npart < 1 || in->nsub < 1 || in->proflen < 2)
@@ -851,96 +810,45 @@ int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* 
   const bool useg = pfd_use_global(h, in);
   if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
     return pfd_shape_err(h, "pfd_dmprof", in);
-  int rc = call_begin(h);
-  if (rc) return rc;
+  if ((rc = call_begin(h))) return rc;
   const pfe::PfdGlobalPlan gp = useg ? pfe::pfd_global_plan(in->nsub, in->proflen, n) : pfe::PfdGlobalPlan();
   hipStream_t st = h->stream;
-  pfe::PfdArgs a;
-  a.npart = in->npart;
-  a.nsub = in->nsub;
-  a.L = in->proflen;
-  a.n = n;
-  a.waves = h->opt.pfd_waves;
-  const size_t np = (size_t)n * in->npart * in->nsub * in->proflen;
+  pfe::PfdArgs a = pfd_args(h, in);
   // split pipeline: two buffers of part sums, chunks of up to 4096 folds
   // (2 x 4096 x nsub x L doubles: 268 MB at 32 x 128)
   const bool split = !useg && h->opt.pfd_split && h->fork.side[0] && pfe::pfd_split_ok(a);
   const int64_t chunk = n < 4096 ? n : 4096;
   // (or the slabs of the global-memory kernel)
-  const size_t wsb = split ? align256(2 * (size_t)chunk * in->nsub * in->proflen * sizeof(double))
-                           : align256(gp.bytes());
-  size_t wsoff = 0;
+  const size_t ws_bytes =
+      split ? 2 * (size_t)chunk * in->nsub * in->proflen * sizeof(double) : gp.bytes();
   if (split) {
     for (hipEvent_t& v : h->pev)
       if (!v) PFE_HIP(h, hipEventCreateWithFlags(&v, hipEventDisableTiming));
   }
-  if (flags & PFE_FLAG_DEVICE_PTRS) {
-    if (wsb) {
-      rc = ensure_scratch(h, wsb);
-      if (rc) return rc;
-    }
-    a.profs = in->profs;
-    a.subfreqs = in->subfreqs;
-    a.scal = in->scal;
-    a.profile = profile;
-    a.chis = chis;
-    a.lyon8 = lyon8;
-    a.status = status;
-  } else {
-    const size_t pb = align256(np * sizeof(double));
-    const size_t fb = align256((size_t)n * in->nsub * sizeof(double));
-    const size_t cb = align256((size_t)n * PFE_PFD_NSCAL * sizeof(double));
-    const size_t ob = profile ? align256((size_t)n * in->proflen * sizeof(double)) : 0;
-    const size_t xb = chis ? align256((size_t)n * PFE_PFD_NDM * sizeof(float)) : 0;
-    const size_t lb = lyon8 ? align256((size_t)n * 8 * sizeof(double)) : 0;
-    const size_t tb = align256((size_t)n * sizeof(uint32_t));
-    rc = ensure_scratch(h, pb + fb + cb + ob + xb + lb + tb + wsb);
-    if (rc) return rc;
-    wsoff = pb + fb + cb + ob + xb + lb + tb;
-    char* base = (char*)h->scratch;
-    size_t off = 0;
-    PFE_HIP(h, hipMemcpyAsync(base, in->profs, np * sizeof(double), hipMemcpyHostToDevice, st));
-    a.profs = (const double*)base;
-    off += pb;
-    PFE_HIP(h, hipMemcpyAsync(base + off, in->subfreqs, (size_t)n * in->nsub * sizeof(double),
-                              hipMemcpyHostToDevice, st));
-    a.subfreqs = (const double*)(base + off);
-    off += fb;
-    PFE_HIP(h, hipMemcpyAsync(base + off, in->scal, (size_t)n * PFE_PFD_NSCAL * sizeof(double),
-                              hipMemcpyHostToDevice, st));
-    a.scal = (const double*)(base + off);
-    off += cb;
-    a.profile = profile ? (double*)(base + off) : nullptr;
-    off += ob;
-    a.chis = chis ? (float*)(base + off) : nullptr;
-    off += xb;
-    a.lyon8 = lyon8 ? (double*)(base + off) : nullptr;
-    off += lb;
-    a.status = (uint32_t*)(base + off);
-  }
+  const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
+  pfe::PfdDmprofStage s;
+  rc = lay_out(h, s, [&](pfe::Arena& A) {
+    return pfe::pfd_dmprof_layout(A, *in, host, profile, chis, lyon8, ws_bytes);
+  });
+  if (rc || (host && (rc = stage_pfd(h, in, s.in, a)))) return rc;
+  a.profile = host ? s.profile : profile;
+  a.chis = host ? s.chis : chis;
+  a.lyon8 = host ? s.lyon8 : lyon8;
+  a.status = host ? s.status : status;
   if (useg) {
-    a.tg = (char*)h->scratch + wsoff;
+    a.tg = s.ws;
     a.gblocks = gp.blocks;
     a.gstride = gp.stride;
   }
-  hipError_t e = split ? pfe::launch_pfd_dmprof_split(a, st, h->fork.side[0],
-                                                      (double*)((char*)h->scratch + wsoff), chunk,
+  hipError_t e = split ? pfe::launch_pfd_dmprof_split(a, st, h->fork.side[0], (double*)s.ws, chunk,
                                                       h->pev)
                        : pfe::launch_pfd_dmprof(a, st);
   if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "pfd_dmprof launch: %s", hipGetErrorString(e));
-  if (!(flags & PFE_FLAG_DEVICE_PTRS)) {
-    if (profile)
-      PFE_HIP(h, hipMemcpyAsync(profile, a.profile, (size_t)n * in->proflen * sizeof(double),
-                                hipMemcpyDeviceToHost, st));
-    if (chis)
-      PFE_HIP(h, hipMemcpyAsync(chis, a.chis, (size_t)n * PFE_PFD_NDM * sizeof(float),
-                                hipMemcpyDeviceToHost, st));
-    if (lyon8)
-      PFE_HIP(h, hipMemcpyAsync(lyon8, a.lyon8, (size_t)n * 8 * sizeof(double),
-                                hipMemcpyDeviceToHost, st));
-    PFE_HIP(h, hipMemcpyAsync(status, a.status, (size_t)n * sizeof(uint32_t),
-                              hipMemcpyDeviceToHost, st));
-    PFE_HIP(h, hipStreamSynchronize(st));
+  if (host) {
+    if ((profile && (rc = fetch(h, profile, a.profile, (size_t)n * in->proflen))) ||
+        (chis && (rc = fetch(h, chis, a.chis, (size_t)n * PFE_PFD_NDM))) ||
+        (rc = fetch_out(h, lyon8, a.lyon8, 8, status, a.status, n)))
+      return rc;
   }
   return call_end(h);
 }
@@ -951,12 +859,9 @@ int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* 
 // columns from column c0 of the 22-score vector, or of the DM-fit inputs par22 when c0 < 0)
 static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
                            uint32_t flags, const char* fn, unsigned groups, int c0, int k) {
-  if (!h) return PFE_EINVAL;
-  h->err.clear();
-  if (!in || !out || !status) return set_err(h, PFE_EINVAL, "%s: null argument", fn);
-  const int64_t n = in->n;
-  if (n < 0) return set_err(h, PFE_EINVAL, "%s: n < 0", fn);
-  if (n == 0) return PFE_OK;
+  int64_t n;
+  int rc = call_check(h, fn, in, out && status, n);
+  if (rc || n == 0) return rc;
   if (!in->profs || !in->subfreqs || !in->scal)
     return set_err(h, PFE_EINVAL, "%s: null input array", fn);
   if (in->npart < 1 || in->nsub < 2 || in->proflen < 8 || in->proflen > 1024)
@@ -965,78 +870,34 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, double* out, uin
   const bool useg = pfd_use_global(h, in);
   if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
     return pfd_shape_err(h, fn, in);
-  int rc = call_begin(h);
-  if (rc) return rc;
+  if ((rc = call_begin(h))) return rc;
   const pfe::PfdGlobalPlan gp = useg ? pfe::pfd_global_plan(in->nsub, in->proflen, n) : pfe::PfdGlobalPlan();
   hipStream_t st = h->stream;
-  pfe::PfdArgs a;
-  a.npart = in->npart;
-  a.nsub = in->nsub;
-  a.L = in->proflen;
-  a.n = n;
-  a.waves = h->opt.pfd_waves;
+  pfe::PfdArgs a = pfd_args(h, in);
   const bool all = groups == pfe::PFD_G_ALL;
   const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
-  const size_t work = pfe::pfd22_workspace_bytes(n, in->proflen, groups);
-  const size_t gb = gp.bytes();  // the slabs of the global-memory kernel, after the workspace
-  const size_t np = (size_t)n * in->npart * in->nsub * in->proflen;
-  // a group call scores into a 22-column scratch of its own and hands out its k columns
-  const size_t sb = all ? 0 : align256((size_t)n * 22 * sizeof(double));
-  double* dout = out;
-  uint32_t* dstat = status;
-  size_t off = 0;
-  if (!host) {
-    rc = ensure_scratch(h, sb + align256(work) + gb);
-    if (rc) return rc;
-    a.profs = in->profs;
-    a.subfreqs = in->subfreqs;
-    a.scal = in->scal;
-  } else {
-    const size_t pb = align256(np * sizeof(double));
-    const size_t fb = align256((size_t)n * in->nsub * sizeof(double));
-    const size_t cb = align256((size_t)n * PFE_PFD_NSCAL * sizeof(double));
-    const size_t ob = align256((size_t)n * k * sizeof(double));
-    const size_t tb = align256((size_t)n * sizeof(uint32_t));
-    rc = ensure_scratch(h, pb + fb + cb + ob + tb + sb + align256(work) + gb);
-    if (rc) return rc;
-    char* base = (char*)h->scratch;
-    PFE_HIP(h, hipMemcpyAsync(base, in->profs, np * sizeof(double), hipMemcpyHostToDevice, st));
-    a.profs = (const double*)base;
-    off += pb;
-    PFE_HIP(h, hipMemcpyAsync(base + off, in->subfreqs, (size_t)n * in->nsub * sizeof(double),
-                              hipMemcpyHostToDevice, st));
-    a.subfreqs = (const double*)(base + off);
-    off += fb;
-    PFE_HIP(h, hipMemcpyAsync(base + off, in->scal, (size_t)n * PFE_PFD_NSCAL * sizeof(double),
-                              hipMemcpyHostToDevice, st));
-    a.scal = (const double*)(base + off);
-    off += cb;
-    dout = (double*)(base + off);
-    off += ob;
-    dstat = (uint32_t*)(base + off);
-    off += tb;
-  }
-  double* d22 = all ? dout : (double*)((char*)h->scratch + off);
-  off += sb;
+  const int cus = pfe::device_cus();
+  pfe::PfdScoresStage s;
+  rc = lay_out(h, s, [&](pfe::Arena& A) {
+    return pfe::pfd_scores_layout(A, *in, host, groups, k, gp.bytes(), cus, h->opt);
+  });
+  if (rc || (host && (rc = stage_pfd(h, in, s.in, a)))) return rc;
+  double* dout = host ? s.out : out;
+  uint32_t* dstat = host ? s.status : status;
+  double* d22 = all ? dout : s.d22;  // a group call scores into a 22-column scratch of its own
   if (useg) {
-    a.tg = (char*)h->scratch + off + align256(work);
+    a.tg = s.tg;
     a.gblocks = gp.blocks;
     a.gstride = gp.stride;
   }
-  char* wk = (char*)h->scratch + off;
-  hipError_t e = pfe::launch_pfd22(a, d22, dstat, wk, work, st, &h->fork, h->opt, groups, !all);
+  hipError_t e = pfe::launch_pfd22(a, d22, dstat, s.work, st, &h->fork, h->opt, groups, !all);
   if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
   if (!all) {
-    const double* par22 = c0 < 0 ? pfe::pfd22_params(wk) : nullptr;
     hipLaunchKernelGGL(k_take_cols, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st,
-                       c0 < 0 ? par22 : d22, c0 < 0 ? 8 : 22, c0 < 0 ? 0 : c0, k, n, dout);
+                       c0 < 0 ? s.work.par22 : d22, c0 < 0 ? 8 : 22, c0 < 0 ? 0 : c0, k, n, dout);
     PFE_HIP(h, hipGetLastError());
   }
-  if (host) {
-    PFE_HIP(h, hipMemcpyAsync(out, dout, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, st));
-    PFE_HIP(h, hipMemcpyAsync(status, dstat, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    PFE_HIP(h, hipStreamSynchronize(st));
-  }
+  if (host && (rc = fetch_out(h, out, dout, k, status, dstat, n))) return rc;
   return call_end(h);
 }
 

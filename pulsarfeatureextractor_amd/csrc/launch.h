@@ -1,0 +1,278 @@
+// launch.h — what crosses translation units below the C-ABI: the launchers, and the layout of
+// every piece of device scratch they and the C-ABI calls (capi.hip) work on.  Each layout is
+// one walk over an Arena (arena.h): measured, then placed once the handle's scratch is large
+// enough.  The layouts make no HIP call (tests/native/layout_driver.cpp runs them on a CPU).
+#pragma once
+
+#include "arena.h"
+#include "bates_common.h"
+#include "pfd.h"
+
+namespace pfe {
+
+// ---- launchers -------------------------------------------------------------------------
+hipError_t launch_lyon8_u8(const uint8_t* prof, int64_t ps, int lp, const uint8_t* dm,
+                           int64_t ds, int ld, int64_t n, double* out, hipStream_t st,
+                           const Options& o);
+hipError_t launch_lyon8_f64(const double* prof, int64_t ps, int lp, const double* dm,
+                            int64_t ds, int ld, int64_t n, double* out, hipStream_t st,
+                            const Options& o);
+hipError_t launch_sine(const BatesArgs& a, hipStream_t st);
+hipError_t launch_gauss(const BatesArgs& a, hipStream_t st);
+hipError_t launch_dmfit(const BatesArgs& a, hipStream_t st);
+hipError_t launch_subband(const BatesArgs& a, hipStream_t st);
+// pfe_subband3: out n x 3; work: subband_work_bytes(n, nsub, lsb) bytes, or null when 0
+hipError_t launch_subband3(const pfe_bates_in* in, double* out, uint32_t* status, void* work,
+                           hipStream_t st);
+const char* subband_shape_error(int nsub, int lsb);
+size_t subband_work_bytes(int64_t n, int nsub, int lsb);
+void launch_clear_internal(uint32_t* status, int64_t n, hipStream_t st);
+bool fork_begin(const Fork* fk, hipStream_t st);
+hipError_t fork_end(const Fork* fk, hipStream_t st);
+int device_cus();  // compute units of the current device (the `cus` of the layouts)
+
+// ---- the 22-score chain's workspace ----------------------------------------------------
+// Fits per wave of the batched kernels: as many as fit the LDS state (32), but few enough
+// that the grid holds ~4 waves for every one of (CUs x 16) wave slots -- each wave runs its
+// fits one after another, so a batch of fewer waves than slots finishes with its slowest wave
+inline int blm_fits_per_wave(int64_t n, int cus) {
+  const int64_t f = n / ((int64_t)cus * 64);
+  return (int)(f < 4 ? 4 : f > BLM_FPW ? BLM_FPW : f);
+}
+
+// persistent waves of the batched and pooled kernels: enough to fill every CU (8 waves
+// each), never more than there are batches
+inline int persistent_waves(int64_t n, int cus) {
+  const int fpw = blm_fits_per_wave(n, cus);
+  const int64_t batches = (n + fpw - 1) / fpw;
+  const int64_t w = (int64_t)cus * 8;
+  return (int)(batches < w ? (batches > 0 ? batches : 1) : w);
+}
+
+// hand-over regions (lm_group.h HandOver) of the three chains: waves x slots x K x group
+// lanes (16; 32 for the profile fits of > 128 bins); the Gaussian chain runs a.pwaves waves,
+// the DM and sine kernels pool_grid(a, 3)
+inline int64_t hand_waves(int64_t n, int region, int cus) {
+  const int64_t cap = (int64_t)cus * (region == HAND_GAUSS ? 8 : 12);
+  return n < 1 ? 1 : n < cap ? n : cap;
+}
+inline size_t hand_doubles(int64_t n, int region, int lp, int cus) {
+  const int k = region == HAND_GAUSS ? HAND_K_GAUSS : region == HAND_DM ? HAND_K_DM : HAND_K_SINE;
+  const int slots = region == HAND_GAUSS ? GDG8_FPW : GLM_FPW;  // the Gaussian chain's widest pool
+  return (size_t)hand_waves(n, region, cus) * slots * k * glm_group_lanes(lp);
+}
+
+// waves of k_ghist_wide (each with a WIDE_SLAB_BYTES = 720 KB scratch slab): one per 64
+// candidates up to 256, so a small batch does not carry 184 MB of slabs for a queue that is
+// usually empty, and a large one still drains a big queue (low-noise data) in parallel
+inline int wide_waves(int64_t n) {
+  const int64_t w = n / 64;
+  return (int)(w < 1 ? 1 : w > 256 ? 256 : w);
+}
+
+// The workspace fields of `a` for a chain over n candidates of lp bins on a device of `cus`
+// compute units: [GaussWS x n][counters][hand-over regions][wide queue][wide slabs][per-wave
+// scratch], then sub_bytes (subband_work_bytes: not 0 for the sub-band shapes the LDS
+// kernels do not hold) of the any-shape sub-band kernel's slabs
+inline void bates_layout(Arena& A, BatesArgs& a, int64_t n, int lp, size_t sub_bytes, int cus,
+                         const Options& o) {
+  static const char* const hand_name[3] = {"hand_gauss", "hand_dm", "hand_sine"};
+  a.cus = cus;
+  a.ws = A.take<GaussWS>((size_t)n, "gauss_ws");
+  a.counters = A.take<unsigned>(BATES_NCOUNTERS, "counters");
+  for (int r = 0; r < 3; ++r) {
+    double* hb = A.take<double>(hand_doubles(n, r, lp, cus), hand_name[r]);
+    a.hand[r] = o.handover ? hb : nullptr;
+  }
+  a.wide_list = A.take<int>((size_t)n, "wide_list");
+  a.wide_waves = wide_waves(n);
+  a.wide_scr = (double*)A.take<char>((size_t)a.wide_waves * WIDE_SLAB_BYTES, "wide_slabs");
+  a.pwaves = persistent_waves(n, cus);
+  a.wscr = A.take<double>((size_t)a.pwaves * gdg_wave_scratch_doubles(lp), "wave_scratch");
+  a.sub_work = nullptr;
+  if (sub_bytes) a.sub_work = A.take<char>(sub_bytes, "sub_work");
+}
+
+// The score groups `groups` (BG_*) of the chain, each into its own columns of out (n x 22);
+// status gets the failure bits of those groups only.  work: the fields bates_layout fills.
+// raw_dm: getDMFittings' signed shift in column 17 (the per-group entry point pfe_dmfit4)
+// instead of the 22-score vector's |shift|.  fprof: the profiles as n x lp doubles (a PFD's
+// float profile: the F = true kernels that launch_pfd22 runs) instead of in->prof, or null.
+hipError_t launch_bates_groups(const pfe_bates_in* in, double* out, uint32_t* status,
+                               const BatesArgs& work, hipStream_t st, const Fork* fk,
+                               const Options& o, unsigned groups, bool raw_dm,
+                               const double* fprof);
+hipError_t launch_bates22(const pfe_bates_in* in, double* out, uint32_t* status,
+                          const BatesArgs& work, hipStream_t st, const Fork* fk,
+                          const Options& o);
+// batching parameters and the Freedman-Diaconis constants of a chain over n candidates of lp
+// bins, on the workspace bates_layout placed in `a`
+void bates_setup(BatesArgs& a, int64_t n, int lp, const Options& o);
+
+// ---- the PFD 22-score chain's workspace (pfd22.hip) --------------------------------------
+struct Pfd22Work {
+  double* profile = nullptr;  // n x L: the whole chain only (no group call fits the profile)
+  float* chis = nullptr;      // n x PFE_PFD_NDM: with PFD_G_DM (the sweep runs for the fit only)
+  double* par22 = nullptr;    // n x 8, the DM-fit inputs [period, snr, dm, width, ...], unfiltered
+  BatesArgs bates;            // with PFD_G_DM
+};
+inline Pfd22Work pfd22_layout(Arena& A, int64_t n, int L, unsigned groups, int cus,
+                              const Options& o) {
+  Pfd22Work w{};
+  if (groups == PFD_G_ALL) w.profile = A.take<double>((size_t)n * L, "profile");
+  if (groups & PFD_G_DM) w.chis = A.take<float>((size_t)n * PFE_PFD_NDM, "chis");
+  w.par22 = A.take<double>((size_t)n * 8, "par22");
+  if (groups & PFD_G_DM) bates_layout(A, w.bates, n, L, 0, cus, o);
+  return w;
+}
+// pa: the PFD inputs (profs, subfreqs, scal, shape, n); out n x 22, status n (device).
+// groups != PFD_G_ALL: only those groups' kernels run and only their columns of out and their
+// status bits are set; raw_dm: getDMFittings' signed shift in column 17
+hipError_t launch_pfd22(PfdArgs pa, double* out, uint32_t* status, const Pfd22Work& w,
+                        hipStream_t st, const Fork* fk, const Options& o,
+                        unsigned groups = PFD_G_ALL, bool raw_dm = false);
+
+// ---- the scratch of one C-ABI call -------------------------------------------------------
+// Host-pointer calls (host = true) stage their inputs, outputs and status first; the
+// launcher's workspace follows.  Device-pointer calls take the workspace only.
+
+// pfe_bates22 (chain: nout = 22, the DM curve, bates_layout) / pfe_subband3 (nout = 3)
+struct ScoreStage {
+  uint8_t *prof = nullptr, *sub = nullptr;
+  double *dmcurve = nullptr, *scal = nullptr, *out = nullptr;
+  uint32_t* status = nullptr;
+  void* sub_work = nullptr;  // pfe_subband3
+  BatesArgs bates;           // pfe_bates22
+};
+inline ScoreStage score_layout(Arena& A, const pfe_bates_in& in, bool host, bool chain,
+                               size_t sub_bytes, int cus, const Options& o) {
+  ScoreStage s{};
+  const size_t n = (size_t)in.n;
+  if (host) {
+    s.prof = A.take<uint8_t>(n * in.lp, "prof");
+    s.sub = A.take<uint8_t>(n * in.nsub * in.lsb, "sub");
+    if (chain) s.dmcurve = A.take<double>(n * in.ndm, "dmcurve");
+    s.scal = A.take<double>(n * PFE_NSCAL, "scal");
+    s.out = A.take<double>(n * (chain ? 22 : 3), "out");
+    s.status = A.take<uint32_t>(n, "status");
+  }
+  if (chain)
+    bates_layout(A, s.bates, in.n, in.lp, sub_bytes, cus, o);
+  else if (sub_bytes)
+    s.sub_work = A.take<char>(sub_bytes, "sub_work");
+  return s;
+}
+
+// one score group of n candidates (groups: BG_SINE / BG_GAUSS / BG_DM; 0: pfe_params4, which
+// fits nothing).  A fit scores into a 22-column scratch d22 and hands out its k columns.
+// Inputs: the DM curves (BG_DM: lp = 0), the float profiles (f64) or the byte profiles, and
+// the scalars of every call but the f64 ones.
+struct GroupStage {
+  uint8_t* prof = nullptr;
+  double *fprof = nullptr, *dmcurve = nullptr, *scal = nullptr, *d22 = nullptr, *out = nullptr;
+  uint32_t* status = nullptr;
+  BatesArgs bates;
+};
+inline GroupStage group_layout(Arena& A, int64_t n_, int lp, int ndm, unsigned groups, bool f64,
+                               int k, bool host, int cus, const Options& o) {
+  GroupStage s{};
+  const size_t n = (size_t)n_;
+  if (host) {
+    if (groups == BG_DM)
+      s.dmcurve = A.take<double>(n * ndm, "dmcurve");
+    else if (f64)
+      s.fprof = A.take<double>(n * lp, "fprof");
+    else if (groups)
+      s.prof = A.take<uint8_t>(n * lp, "prof");
+    if (!f64) s.scal = A.take<double>(n * PFE_NSCAL, "scal");
+  }
+  if (groups) s.d22 = A.take<double>(n * 22, "d22");
+  if (host) {
+    s.out = A.take<double>(n * k, "out");
+    s.status = A.take<uint32_t>(n, "status");
+  }
+  if (groups) bates_layout(A, s.bates, n_, lp, 0, cus, o);
+  return s;
+}
+
+// the three inputs every PFD call stages
+struct PfdInputs {
+  double *profs = nullptr, *subfreqs = nullptr, *scal = nullptr;
+};
+inline PfdInputs pfd_inputs_layout(Arena& A, const pfe_pfd_in& in) {
+  PfdInputs s;
+  const size_t n = (size_t)in.n;
+  s.profs = A.take<double>(n * in.npart * in.nsub * in.proflen, "profs");
+  s.subfreqs = A.take<double>(n * in.nsub, "subfreqs");
+  s.scal = A.take<double>(n * PFE_PFD_NSCAL, "scal");
+  return s;
+}
+
+// pfe_pfd_dmprof: the outputs the caller asked for, then ws_bytes for the two part-sum
+// buffers of the split pipeline or the slabs of the global-memory kernel (PfdGlobalPlan)
+struct PfdDmprofStage {
+  PfdInputs in;
+  double* profile = nullptr;
+  float* chis = nullptr;
+  double* lyon8 = nullptr;
+  uint32_t* status = nullptr;
+  void* ws = nullptr;
+};
+inline PfdDmprofStage pfd_dmprof_layout(Arena& A, const pfe_pfd_in& in, bool host, bool profile,
+                                        bool chis, bool lyon8, size_t ws_bytes) {
+  PfdDmprofStage s;
+  const size_t n = (size_t)in.n;
+  if (host) {
+    s.in = pfd_inputs_layout(A, in);
+    if (profile) s.profile = A.take<double>(n * in.proflen, "profile");
+    if (chis) s.chis = A.take<float>(n * PFE_PFD_NDM, "chis");
+    if (lyon8) s.lyon8 = A.take<double>(n * 8, "lyon8");
+    s.status = A.take<uint32_t>(n, "status");
+  }
+  if (ws_bytes) s.ws = A.take<char>(ws_bytes, "ws");
+  return s;
+}
+
+// pfe_pfd_bates22 (groups = PFD_G_ALL, k = 22) and the PFD group calls, which score into a
+// 22-column scratch d22 of their own and hand out k columns; g_bytes: the slabs of the
+// global-memory kernel (0: the fold lives in LDS)
+struct PfdScoresStage {
+  PfdInputs in;
+  double *out = nullptr, *d22 = nullptr;
+  uint32_t* status = nullptr;
+  Pfd22Work work;
+  void* tg = nullptr;
+};
+inline PfdScoresStage pfd_scores_layout(Arena& A, const pfe_pfd_in& in, bool host,
+                                        unsigned groups, int k, size_t g_bytes, int cus,
+                                        const Options& o) {
+  PfdScoresStage s;
+  const size_t n = (size_t)in.n;
+  if (host) {
+    s.in = pfd_inputs_layout(A, in);
+    s.out = A.take<double>(n * k, "out");
+    s.status = A.take<uint32_t>(n, "status");
+  }
+  if (groups != PFD_G_ALL) s.d22 = A.take<double>(n * 22, "d22");
+  s.work = pfd22_layout(A, in.n, in.proflen, groups, cus, o);
+  if (g_bytes) s.tg = A.take<char>(g_bytes, "tg");
+  return s;
+}
+
+// one slot of the chunked Lyon-8 host pipeline: `chunk` rows in, their features out (the
+// device slots and the pinned staging ring share the layout)
+template <typename T>
+struct Lyon8Slot {
+  T *prof = nullptr, *dm = nullptr;
+  double* out = nullptr;
+};
+template <typename T>
+inline Lyon8Slot<T> lyon8_slot_layout(Arena& A, int64_t chunk, int lp, int ld) {
+  Lyon8Slot<T> s;
+  s.prof = A.take<T>((size_t)chunk * lp, "prof");
+  s.dm = A.take<T>((size_t)chunk * ld, "dm");
+  s.out = A.take<double>((size_t)chunk * 8, "out");
+  return s;
+}
+
+}  // namespace pfe

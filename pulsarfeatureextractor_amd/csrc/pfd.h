@@ -67,16 +67,6 @@ struct PfdGlobalPlan {
 PfdGlobalPlan pfd_global_plan(int nsub, int L, int64_t n);
 hipError_t launch_pfd_dmprof_g(const PfdArgs& a, hipStream_t st);  // pfd_global.hip
 hipError_t launch_pfd_dmprof(const PfdArgs& a, hipStream_t st);
-// the 22-score chain (pfd22.hip); work: pfd22_workspace_bytes(n, L, groups) bytes of device
-// memory.  groups != PFD_G_ALL: only those groups' kernels run and only their columns of out
-// (n x 22) and their status bits are set; raw_dm: getDMFittings' signed shift in column 17
-size_t pfd22_workspace_bytes(int64_t n, int L, unsigned groups = PFD_G_ALL);
-// the DM-fit inputs par22 (n x 8: [period, snr, dm, width, ...], unfiltered) that a launch
-// without PFD_G_DM leaves in its workspace
-const double* pfd22_params(const void* work);
-struct Fork;
-hipError_t launch_pfd22(PfdArgs a, double* out, uint32_t* status, void* work, size_t work_bytes,
-                        hipStream_t st, const Fork* fk, const Options& o,
-                        unsigned groups = PFD_G_ALL, bool raw_dm = false);
+// the 22-score chain (pfd22.hip): launch_pfd22 and its workspace are in launch.h
 
 }  // namespace pfe

@@ -12,22 +12,13 @@
 // runs k_pfd_dmprof for that group only, and the DM fit only for PFD_G_DM.
 #include <cmath>
 
-#include "bates_common.h"
+#include "launch.h"
 #include "lm_batch.h"
 #include "lm_group.h"
-#include "pfd.h"
 
 namespace pfe {
 
 #pragma clang fp contract(off)
-
-hipError_t launch_sine(const BatesArgs& a, hipStream_t st);
-hipError_t launch_gauss(const BatesArgs& a, hipStream_t st);
-size_t bates22_workspace_bytes(const pfe_bates_in* in);
-void bates_setup(BatesArgs& a, int64_t n, int lp, void* work, const Options& o);
-void launch_clear_internal(uint32_t* status, int64_t n, hipStream_t st);
-bool fork_begin(const Fork* fk, hipStream_t st);
-hipError_t fork_end(const Fork* fk, hipStream_t st);
 
 constexpr double KDM_PFD = 8.3 * 1000000.0;  // 8.3*10**6      (PFDOperations.py:342)
 constexpr double DF_PFD = 32.0;              // df = 32         (:343)
@@ -324,68 +315,37 @@ __global__ __launch_bounds__(64, 2) void k_pfd_dmfitg(PfdDMArgs d) {
   glm_engine<4, 4 * MPL, FPW>(prob, S, T.ph, T.list, d.a.hand[HAND_DM], HAND_K_DM);
 }
 
-size_t pfd22_workspace_bytes(int64_t n, int L, unsigned groups) {
-  pfe_bates_in in{};
-  in.n = n;
-  in.lp = L;
-  const size_t al = 255;
-  // the parameters or the sub-band scores alone: par22 and no fit
-  if (!(groups & PFD_G_DM)) return ((size_t)n * 8 * sizeof(double) + al) + 256;
-  return bates22_workspace_bytes(&in) + ((size_t)n * L * sizeof(double) + al) +
-         ((size_t)n * PFE_PFD_NDM * sizeof(float) + al) + ((size_t)n * 8 * sizeof(double) + al) +
-         256;
-}
-
-static char* carve(char*& p, size_t bytes) {
-  char* r = (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-  p = r + bytes;
-  return r;
-}
-
-const double* pfd22_params(const void* work) {
-  char* p = (char*)work;
-  return (const double*)carve(p, 0);  // launch_pfd22 carves par22 first when no fit runs
-}
-
-// pa: the PFD inputs (profs, subfreqs, scal, shape, n); out n x 22, status n (device)
-hipError_t launch_pfd22(PfdArgs pa, double* out, uint32_t* status, void* work, size_t work_bytes,
+hipError_t launch_pfd22(PfdArgs pa, double* out, uint32_t* status, const Pfd22Work& w,
                         hipStream_t st, const Fork* fk, const Options& o, unsigned groups,
                         bool raw_dm) {
   const int64_t n = pa.n;
-  const int L = pa.L;
-  if (work_bytes < pfd22_workspace_bytes(n, L, groups)) return hipErrorInvalidValue;
   const bool all = groups == PFD_G_ALL, dm = (groups & PFD_G_DM) != 0;
-  char* p = (char*)work;
-  // one group: no profile leaves the kernel (the fits on it are not run), and the sweep
-  // runs only for the DM fit (the kernels skip it when chis and lyon8 are null)
-  double* profile = all ? (double*)carve(p, (size_t)n * L * sizeof(double)) : nullptr;
-  float* chis = dm ? (float*)carve(p, (size_t)n * PFE_PFD_NDM * sizeof(float)) : nullptr;
-  double* par22 = (double*)carve(p, (size_t)n * 8 * sizeof(double));
-  char* bwork = carve(p, 0);
   hipError_t e = hipMemsetAsync(out, 0, (size_t)n * 22 * sizeof(double), st);
   if (e != hipSuccess) return e;
-  pa.profile = profile;
-  pa.chis = chis;
+  // one group: no profile leaves the kernel (the fits on it are not run), and the sweep
+  // runs only for the DM fit (the kernels skip it when chis and lyon8 are null)
+  pa.profile = w.profile;
+  pa.chis = w.chis;
   pa.lyon8 = nullptr;
   pa.status = status;
   pa.out22 = out;
-  pa.par22 = par22;
+  pa.par22 = w.par22;
   pa.groups = groups;
   if ((e = launch_pfd_dmprof(pa, st)) != hipSuccess) return e;
   if (!dm) {
     launch_clear_internal(status, n, st);
     return hipGetLastError();
   }
-  BatesArgs a;
-  bates_setup(a, n, L, bwork, o);
+  BatesArgs a = w.bates;
+  bates_setup(a, n, pa.L, o);
   a.prof = nullptr;
-  a.fprof = profile;
+  a.fprof = w.profile;
   a.sub = nullptr;
   a.nsub = 0;
   a.lsb = 0;
   a.dmcurve = nullptr;
   a.ndm = PFE_PFD_NDM;
-  a.scal = par22;
+  a.scal = w.par22;
   a.out = out;
   a.status = status;
   a.raw_dm = raw_dm ? 1 : 0;
@@ -395,7 +355,7 @@ hipError_t launch_pfd22(PfdArgs pa, double* out, uint32_t* status, void* work, s
   const bool forked = all && fork_begin(fk, st);
   const hipStream_t sg = forked ? fk->side[0] : st, sd = forked ? fk->side[1] : st;
   if (all && (e = launch_gauss(a, sg)) != hipSuccess) return e;
-  const PfdDMArgs d{a, chis};
+  const PfdDMArgs d{a, w.chis};
   if (a.solver == PFE_SOLVER_POOLED)  // pooled group-LM unless the handle selects another solver
     hipLaunchKernelGGL((k_pfd_dmfitg<2>), dim3((unsigned)a.pwaves), dim3(64), 0, sd, d);
   else

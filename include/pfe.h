@@ -135,6 +135,10 @@ int pfe_synchronize(pfe_handle* h);
  *   PFE_OPT_PFD_GLOBAL   PFD preprocessing: 0 (default) = folds whose sub-band profiles fit the
  *                        LDS stay on chip and every other shape goes through global scratch of
  *                        the handle; 1 = every shape through global scratch (same bits)
+ *   PFE_OPT_SUBF64_GLOBAL  pfe_subband3_f64 / pfe_bates22_f64: 0 (default) = candidates whose
+ *                        sub-bands fit the LDS stay on chip and every other shape goes through
+ *                        per-wave slabs of the handle's scratch; 1 = every shape through the
+ *                        slabs (same bits)
  * Returns PFE_EINVAL for an unknown option or an out-of-range value.
  * --------------------------------------------------------------------------------------- */
 #define PFE_OPT_SOLVER 1
@@ -148,6 +152,7 @@ int pfe_synchronize(pfe_handle* h);
 #define PFE_OPT_PFD_SPLIT 9
 #define PFE_OPT_LYON8_DM_SPLIT 10
 #define PFE_OPT_PFD_GLOBAL 11
+#define PFE_OPT_SUBF64_GLOBAL 12
 #define PFE_SOLVER_POOLED 0
 #define PFE_SOLVER_BATCHED 1
 #define PFE_SOLVER_WAVE 2
@@ -278,6 +283,61 @@ int pfe_sinusoid4_f64(pfe_handle* h, const double* prof, int32_t lp, int64_t n, 
                       uint32_t* status, uint32_t flags);
 int pfe_gauss7_f64(pfe_handle* h, const double* prof, int32_t lp, int64_t n, double* out,
                    uint32_t* status, uint32_t flags);
+
+/* A folded candidate held as float arrays (another fold format, normalised or baseline-
+ * subtracted PHCX data, the dedispersed sub-bands of a fold): the sub-band scores and the
+ * whole 22-score vector.
+ *   prof    : n x lp fp64 profile
+ *   sub     : n x nsub x lsb fp64 sub-bands
+ *   dmcurve : n x ndm fp64 reduced DM curve, as for pfe_bates22
+ *   scal    : n x PFE_NSCAL fp64, as for pfe_bates22
+ * Dense rows, 8-byte aligned; host or device pointers as the flags say.  `sub` is never
+ * written: a candidate is scored on a copy (its own LDS partition or scratch slab).
+ *
+ *   pfe_subband3_f64 <- PHCXOperations.getSubbandParameters        PHCXOperations.py:305-349
+ *                       (getSubband_scores ProfileOperations.py:1585-1686, getProfileCorr
+ *                        PHCXOperations.py:387-415) on float arrays, with the arithmetic of
+ *                       PFDOperations.getSubbandParameters (PFDOperations.py:401-466)
+ * Reads prof, sub and scal[PFE_SCAL_WIDTH] (dmcurve / ndm are ignored and may be NULL / 0);
+ * out = n x 3 fp64 [s20, s21, s22]: boxcar sums of wb = ceil(width * lsb) bins added left to
+ * right from 0 (:1608-1617), each band's first strict maximum above -10000.0 with max_bin
+ * carried across the bands (:1619-1628), the RMS rule (:1629-1651), the mean of the pair
+ * correlations that are not NaN (:1653-1677) and the sum of |corrcoef(band, profile)| >
+ * 0.0055.  s20 holds the reference's bits, s21 and s22 are within 1e-12 relative (numpy's dots
+ * run in BLAS order).  status = PFE_ST_SUBBAND_FAIL, and out = 0, where the reference raises:
+ * no window (wb > lsb), wb <= 0, a NaN or infinite width, no valid pair, nsub == 1,
+ * lp != lsb.
+ * Shapes: nsub >= 1, lsb >= 1 and lp >= 1 with the per-candidate vectors
+ *   (2 * lsb + 3 * nsub) * 8 bytes, rounded up to 16,  <=  163840 bytes (160 KiB of LDS),
+ * so every nsub <= 1024 with lsb <= 2048; beyond that PFE_EINVAL.  A candidate whose
+ * nsub * lsb doubles (rounded up to 16 bytes) fit the LDS beside those vectors is scored on
+ * chip, several waves to a block; every other shape, and every shape under
+ * PFE_OPT_SUBF64_GLOBAL = 1, in a per-wave slab of the handle's scratch (at most 1 GiB of
+ * slabs), with the same bits.
+ *
+ *   pfe_bates22_f64  <- PHCXFile.compute                           PHCXFile.py:383-409
+ * out = n x 22: columns 0-3 the bits of pfe_sinusoid4_f64(prof), 4-10 of pfe_gauss7_f64(prof),
+ * 11-14 pfe_params4 with filterScore(13/14) applied as pfe_bates22 applies it, 15-18
+ * pfe_dmfit4 with s18 = |Shift|, 19-21 the bits of pfe_subband3_f64; status the OR of the
+ * groups' bits.  8 <= lp <= 1024 and 3 <= ndm <= 1024 (the fits), the sub-band shapes above.
+ * The groups run on the handle's side streams (PFE_OPT_SERIAL, PFE_OPT_SOLVER as for
+ * pfe_bates22) and are joined before the call returns. */
+typedef struct pfe_bates_f64_in {
+  const double* prof;    /* n x lp */
+  int32_t lp;
+  const double* sub;     /* n x nsub x lsb */
+  int32_t nsub;
+  int32_t lsb;
+  const double* dmcurve; /* n x ndm */
+  int32_t ndm;
+  const double* scal;    /* n x PFE_NSCAL */
+  int64_t n;
+} pfe_bates_f64_in;
+
+int pfe_subband3_f64(pfe_handle* h, const pfe_bates_f64_in* in, double* out, uint32_t* status,
+                     uint32_t flags);
+int pfe_bates22_f64(pfe_handle* h, const pfe_bates_f64_in* in, double* out, uint32_t* status,
+                    uint32_t flags);
 
 /* ---- PFD (PRESTO fold) files: preprocessing + Lyon features -------------------------
  * pfe_pfd_dmprof <- what a freshly loaded PFDFile computes for the dmprof path

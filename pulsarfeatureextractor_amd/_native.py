@@ -49,6 +49,8 @@ EXPORTED_SYMBOLS = (
     "pfe_dmfit4",
     "pfe_sinusoid4_f64",
     "pfe_gauss7_f64",
+    "pfe_subband3_f64",
+    "pfe_bates22_f64",
     "pfe_pfd_dmprof",
     "pfe_pfd_bates22",
     "pfe_pfd_params4",
@@ -86,6 +88,7 @@ OPTIONS = {
     "pfd_split": 9,     # 0 fused kernel (default), 1 part sums streamed beside the sweep
     "lyon8_dm_split": 10,  # 1 (default) chain splits + paired one-chunk rows, 2 splits only, 0 off
     "pfd_global": 11,   # 0 folds that fit stay in LDS (default), 1 every fold through global scratch
+    "subf64_global": 12,  # float sub-bands: 0 shapes that fit stay in LDS (default), 1 all in scratch
 }
 SOLVERS = {"pooled": 0, "batched": 1, "wave": 2}
 
@@ -106,6 +109,10 @@ class BatesIn(C.Structure):
         ("scal", C.c_void_p),
         ("n", C.c_int64),
     ]
+
+
+class BatesF64In(BatesIn):
+    """pfe_bates_f64_in: the fields of pfe_bates_in, prof and sub pointing at doubles."""
 
 
 class PfdIn(C.Structure):
@@ -190,6 +197,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         bates = [vp, ptr(BatesIn), vp, vp, u32]
         pfd = [vp, ptr(PfdIn), vp, vp, u32]
         f64 = [vp, vp, i32, i64, vp, vp, u32]
+        bates_f64 = [vp, ptr(BatesF64In), vp, vp, u32]
         signatures = {  # name: (restype, argtypes), as include/pfe.h and include/pfe_io.h declare
             "pfe_abi_version": (rc, []), "pfe_device_count": (rc, []),
             "pfe_create": (rc, [C.c_int, ptr(vp)]), "pfe_destroy": (None, [vp]),
@@ -202,6 +210,7 @@ def load_library(path: str | None = None) -> C.CDLL:
             "pfe_sinusoid4": (rc, bates), "pfe_gauss7": (rc, bates),
             "pfe_params4": (rc, bates), "pfe_dmfit4": (rc, bates),
             "pfe_sinusoid4_f64": (rc, f64), "pfe_gauss7_f64": (rc, f64),
+            "pfe_subband3_f64": (rc, bates_f64), "pfe_bates22_f64": (rc, bates_f64),
             "pfe_pfd_dmprof": (rc, [vp, ptr(PfdIn), vp, vp, vp, vp, u32]),
             "pfe_pfd_bates22": (rc, pfd), "pfe_pfd_params4": (rc, pfd),
             "pfe_pfd_dmfit4": (rc, pfd), "pfe_pfd_subband3": (rc, pfd),
@@ -573,6 +582,59 @@ class Engine:
     def gauss7_f64(self, prof, out=None, status=None):
         """getGaussianFittings on float profiles (pfe_gauss7_f64) -> ((n, 7) s5-s11, status)."""
         return self._group_f64("pfe_gauss7_f64", 7, prof, out, status)
+
+    # ---- candidates held as float arrays (pfe.h pfe_bates_f64_in) ------------------------
+    def _bates_f64_args(self, fn, prof, sub, dmcurve, scal, with_dm):
+        if prof.ndim != 2 or sub.ndim != 3 or scal.ndim != 2 or scal.shape[1] != PFE_NSCAL:
+            raise ValueError("prof must be (n,lp), sub (n,nsub,lsb), scal (n,%d)" % PFE_NSCAL)
+        n = prof.shape[0]
+        if sub.shape[0] != n or scal.shape[0] != n:
+            raise ValueError("inputs must have the same number of rows")
+        if with_dm and (dmcurve.ndim != 2 or dmcurve.shape[0] != n):
+            raise ValueError("dmcurve must be (n, ndm)")
+        arrays = [("prof", prof), ("sub", sub), ("scal", scal)] + ([("dmcurve", dmcurve)] if with_dm else [])
+        dev = _is_device(prof)
+        if dev:
+            import torch
+
+            for nm, a in arrays:  # dense rows only: a strided tensor is refused, never copied
+                self._dev(a, nm, (torch.float64,))
+            self._follow_torch()
+        else:
+            for nm, a in arrays:
+                if not isinstance(a, np.ndarray) or (nm in ("prof", "sub") and a.dtype != np.float64):
+                    raise TypeError(f"{fn}: {nm}: float64 numpy rows expected (byte candidates go "
+                                    "through subband3 / bates22)")
+            prof, sub, scal = (np.ascontiguousarray(a, dtype=np.float64) for a in (prof, sub, scal))
+            if with_dm:
+                dmcurve = np.ascontiguousarray(dmcurve, dtype=np.float64)
+        bi = BatesF64In(
+            _ptr(prof), prof.shape[1], _ptr(sub), sub.shape[1], sub.shape[2],
+            _ptr(dmcurve) if with_dm else None, dmcurve.shape[1] if with_dm else 0,
+            _ptr(scal), n,
+        )
+        return bi, dev, (prof, sub, dmcurve, scal)
+
+    def subband3_f64(self, prof, sub, scal, out=None, status=None):
+        """Scores 20-22 of candidates held as float arrays (pfe_subband3_f64): prof (n, lp),
+        sub (n, nsub, lsb), scal (n, 8), all float64 -> ((n, 3) float64, (n,) status).  Host
+        arrays of any strides are made dense; device tensors must be contiguous.  `sub` is
+        never written."""
+        bi, dev, keep = self._bates_f64_args("subband3_f64", prof, sub, None, scal, False)
+        out, status, flags = self._outputs(dev, keep[0], bi.n, 3, out, status)
+        self._check(self.lib.pfe_subband3_f64(self._h, C.byref(bi), _ptr(out), _ptr(status), flags))
+        del keep
+        return out, status
+
+    def bates22_f64(self, prof, sub, dmcurve, scal, out=None, status=None):
+        """The 22 scores of candidates held as float arrays (pfe_bates22_f64): the columns of
+        sinusoid4_f64, gauss7_f64, params4 (filtered), dmfit4 (|Shift|) and subband3_f64
+        -> ((n, 22) float64, (n,) status)."""
+        bi, dev, keep = self._bates_f64_args("bates22_f64", prof, sub, dmcurve, scal, True)
+        out, status, flags = self._outputs(dev, keep[0], bi.n, 22, out, status)
+        self._check(self.lib.pfe_bates22_f64(self._h, C.byref(bi), _ptr(out), _ptr(status), flags))
+        del keep
+        return out, status
 
     def features30(self, prof, lyon_dm, sub, dmcurve, scal, out=None):
         """Config 5's feature matrix: the 8 Lyon features (profile + Lyon DM rows) then the

@@ -321,6 +321,10 @@ int pfe_set_option(pfe_handle* h, int32_t option, int64_t v) {
       if (v != 0 && v != 1) break;
       o.pfd_global = (int)v;
       return PFE_OK;
+    case PFE_OPT_SUBF64_GLOBAL:
+      if (v != 0 && v != 1) break;
+      o.subf64_global = (int)v;
+      return PFE_OK;
     default:
       return set_err(h, PFE_EINVAL, "pfe_set_option: unknown option %d", option);
   }
@@ -343,6 +347,7 @@ int pfe_get_option(const pfe_handle* h, int32_t option, int64_t* v) {
     case PFE_OPT_PFD_SPLIT: *v = o.pfd_split; return PFE_OK;
     case PFE_OPT_LYON8_DM_SPLIT: *v = o.lyon8_dm_split; return PFE_OK;
     case PFE_OPT_PFD_GLOBAL: *v = o.pfd_global; return PFE_OK;
+    case PFE_OPT_SUBF64_GLOBAL: *v = o.subf64_global; return PFE_OK;
     default: return PFE_EINVAL;
   }
 }
@@ -755,6 +760,80 @@ int pfe_params4(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* st
   PFE_HIP(h, hipGetLastError());
   if (host && (rc = fetch_out(h, out, dout, 4, status, dstat, n))) return rc;
   return call_end(h);
+}
+
+}  // extern "C"
+
+// ---- float sub-bands and the float 22-score call ------------------------------------------
+// pfe_subband3_f64 (chain = false: out n x 3) and pfe_bates22_f64 (chain: the 22 scores): on
+// the host path the inputs go to the scratch and the results come back; the launchers of
+// subband_f64.hip work behind them
+static int score_f64_call(pfe_handle* h, const pfe_bates_f64_in* in, double* out, uint32_t* status,
+                          uint32_t flags, const char* fn, bool chain) {
+  int64_t n;
+  int rc = call_check(h, fn, in, out && status, n);
+  if (rc || n == 0) return rc;
+  if (!in->prof || !in->sub || !in->scal || (chain && !in->dmcurve))
+    return set_err(h, PFE_EINVAL, "%s: null input array", fn);
+  if ((((uintptr_t)in->prof | (uintptr_t)in->sub | (uintptr_t)in->scal | (uintptr_t)out) & 7) ||
+      (chain && ((uintptr_t)in->dmcurve & 7)))
+    return set_err(h, PFE_EINVAL, "%s: array not 8-byte aligned", fn);
+  if (chain ? (in->lp < 8 || in->lp > 1024) : in->lp < 1)
+    return set_err(h, PFE_EINVAL, "%s: lp=%d outside [%d,%d]", fn, in->lp, chain ? 8 : 1,
+                   chain ? 1024 : INT32_MAX);
+  if (chain && (in->ndm < 3 || in->ndm > 1024))
+    return set_err(h, PFE_EINVAL, "%s: ndm=%d outside [3,1024]", fn, in->ndm);
+  if (in->nsub < 1 || in->lsb < 1)
+    return set_err(h, PFE_EINVAL, "%s: sub-band shape %dx%d", fn, in->nsub, in->lsb);
+  if (!pfe::subf64_plan(in->nsub, in->lsb, n, 1, false).ok)
+    return set_err(h, PFE_EINVAL,
+                   "%s: sub-band shape %dx%d unsupported: the per-candidate vectors "
+                   "((2*lsb + 3*nsub) doubles = %zu bytes) exceed %zu bytes of LDS",
+                   fn, in->nsub, in->lsb, pfe::subf64_vec_bytes(in->nsub, in->lsb),
+                   pfe::SUBF64_LDS_LIMIT);
+  if ((rc = call_begin(h))) return rc;
+  const int cus = pfe::device_cus();
+  const pfe::SubF64Plan p = pfe::subf64_plan(in->nsub, in->lsb, n, cus, h->opt.subf64_global != 0);
+  const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
+  pfe::SubF64Stage s;
+  rc = lay_out(h, s, [&](pfe::Arena& A) {
+    return pfe::subband_f64_layout(A, *in, host, chain, p.slab_bytes(), cus, h->opt);
+  });
+  if (rc) return rc;
+  pfe_bates_f64_in din = *in;
+  if (host) {
+    const size_t m = (size_t)n;
+    if ((rc = stage_in(h, s.prof, in->prof, m * in->lp)) ||
+        (rc = stage_in(h, s.sub, in->sub, m * in->nsub * in->lsb)) ||
+        (chain && (rc = stage_in(h, s.dmcurve, in->dmcurve, m * in->ndm))) ||
+        (rc = stage_in(h, s.scal, in->scal, m * PFE_NSCAL)))
+      return rc;
+    din.prof = s.prof;
+    din.sub = s.sub;
+    if (chain) din.dmcurve = s.dmcurve;
+    din.scal = s.scal;
+  }
+  double* dout = host ? s.out : out;
+  uint32_t* dstat = host ? s.status : status;
+  hipStream_t st = h->stream;
+  hipError_t e = chain ? pfe::launch_bates22_f64(&din, dout, dstat, s.bates, p, s.slabs, st,
+                                                 &h->fork, h->opt)
+                       : pfe::launch_subband_f64(&din, dout, 3, dstat, false, p, s.slabs, st);
+  if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
+  if (host && (rc = fetch_out(h, out, dout, chain ? 22 : 3, status, dstat, n))) return rc;
+  return call_end(h);
+}
+
+extern "C" {
+
+int pfe_subband3_f64(pfe_handle* h, const pfe_bates_f64_in* in, double* out, uint32_t* status,
+                     uint32_t flags) {
+  return score_f64_call(h, in, out, status, flags, "subband3_f64", false);
+}
+
+int pfe_bates22_f64(pfe_handle* h, const pfe_bates_f64_in* in, double* out, uint32_t* status,
+                    uint32_t flags) {
+  return score_f64_call(h, in, out, status, flags, "bates22_f64", true);
 }
 
 // ---- PFD -------------------------------------------------------------------------------

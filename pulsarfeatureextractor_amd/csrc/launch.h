@@ -163,6 +163,90 @@ inline ScoreStage score_layout(Arena& A, const pfe_bates_in& in, bool host, bool
   return s;
 }
 
+// ---- float sub-bands: pfe_subband3_f64 / pfe_bates22_f64 (subband_f64.hip) ---------------
+// One wave scores one candidate: its nsub x lsb doubles T and the per-candidate vectors (the
+// profile, the centred profile / boxcar row, three nsub-vectors) in the wave's partition of the
+// LDS, or -- when that does not fit, or under PFE_OPT_SUBF64_GLOBAL -- T in the wave's slab of
+// global scratch and only the vectors on chip.  Pure arithmetic on the shape (no HIP call).
+constexpr size_t SUBF64_LDS_LIMIT = 160 * 1024;  // the LDS one workgroup can hold (gfx950)
+constexpr int SUBF64_MAX_WPB = 8;                // waves per block
+constexpr size_t SUBF64_SLAB_BUDGET = (size_t)1 << 30;
+struct SubF64Plan {
+  bool ok = false;      // false: the per-candidate vectors alone exceed the LDS
+  bool global = false;  // T in global scratch
+  size_t wave_lds = 0;  // LDS bytes per wave (a multiple of 16)
+  size_t t_lds = 0;     // of which T, in front (0: global)
+  size_t slab = 0;      // bytes per wave's slab (a multiple of 256; 0: on chip)
+  int wpb = 0;          // waves per block
+  int blocks = 0;       // persistent blocks
+  size_t slab_bytes() const { return slab * (size_t)wpb * (size_t)blocks; }
+};
+inline size_t subf64_vec_bytes(int nsub, int lsb) {
+  return ((2 * (size_t)lsb + 3 * (size_t)nsub) * sizeof(double) + 15) & ~(size_t)15;
+}
+inline SubF64Plan subf64_plan(int nsub, int lsb, int64_t n, int cus, bool force_global) {
+  SubF64Plan p;
+  if (nsub < 1 || lsb < 1) return p;
+  const size_t vec = subf64_vec_bytes(nsub, lsb);
+  if (vec > SUBF64_LDS_LIMIT) return p;
+  p.ok = true;
+  const size_t t = ((size_t)nsub * lsb * sizeof(double) + 15) & ~(size_t)15;
+  p.global = force_global || t + vec > SUBF64_LDS_LIMIT;
+  p.t_lds = p.global ? 0 : t;
+  p.wave_lds = p.t_lds + vec;
+  int64_t wpb = (int64_t)(SUBF64_LDS_LIMIT / p.wave_lds);
+  if (wpb > SUBF64_MAX_WPB) wpb = SUBF64_MAX_WPB;
+  // as many blocks per CU as the LDS holds, up to 32 waves
+  int64_t per_cu = (int64_t)(SUBF64_LDS_LIMIT / ((size_t)wpb * p.wave_lds));
+  if (per_cu > 32 / wpb) per_cu = 32 / wpb;
+  int64_t blocks = (int64_t)(cus > 0 ? cus : 1) * per_cu;
+  if (blocks > (n + wpb - 1) / wpb) blocks = (n + wpb - 1) / wpb;
+  if (p.global) {
+    p.slab = ((size_t)nsub * lsb * sizeof(double) + 255) & ~(size_t)255;
+    const int64_t budget = (int64_t)(SUBF64_SLAB_BUDGET / p.slab);  // >= 1 for every ok shape
+    if (wpb > budget) wpb = budget > 0 ? budget : 1;
+    if (blocks * wpb > budget) blocks = budget / wpb;
+  }
+  p.wpb = (int)wpb;
+  p.blocks = (int)(blocks < 1 ? 1 : blocks);
+  return p;
+}
+// scores 20-22 of n candidates into out[c * ldo + 0..2].  chain: a failed row ORs
+// PFE_ST_SUBBAND_FAIL into status and leaves out alone (the 22-score call zeroed both); else
+// every row's status and scores are stored (0.0 where it failed).  slabs: p.slab_bytes() bytes
+hipError_t launch_subband_f64(const pfe_bates_f64_in* in, double* out, int ldo, uint32_t* status,
+                              bool chain, const SubF64Plan& p, void* slabs, hipStream_t st);
+// pfe_bates22_f64: the four fitted / copied groups by the float-profile kernels of the chain
+// and launch_subband_f64, forked over the side streams as launch_bates22 forks its groups
+hipError_t launch_bates22_f64(const pfe_bates_f64_in* in, double* out, uint32_t* status,
+                              const BatesArgs& work, const SubF64Plan& p, void* slabs,
+                              hipStream_t st, const Fork* fk, const Options& o);
+
+// pfe_subband3_f64 (chain = false: nout = 3) / pfe_bates22_f64 (chain: nout = 22, the DM curve,
+// bates_layout): the staged host arrays, then the per-wave slabs of the global path
+struct SubF64Stage {
+  double *prof = nullptr, *sub = nullptr, *dmcurve = nullptr, *scal = nullptr, *out = nullptr;
+  uint32_t* status = nullptr;
+  BatesArgs bates;  // pfe_bates22_f64
+  void* slabs = nullptr;
+};
+inline SubF64Stage subband_f64_layout(Arena& A, const pfe_bates_f64_in& in, bool host, bool chain,
+                                      size_t slab_bytes, int cus, const Options& o) {
+  SubF64Stage s{};
+  const size_t n = (size_t)in.n;
+  if (host) {
+    s.prof = A.take<double>(n * in.lp, "prof");
+    s.sub = A.take<double>(n * in.nsub * in.lsb, "sub");
+    if (chain) s.dmcurve = A.take<double>(n * in.ndm, "dmcurve");
+    s.scal = A.take<double>(n * PFE_NSCAL, "scal");
+    s.out = A.take<double>(n * (chain ? 22 : 3), "out");
+    s.status = A.take<uint32_t>(n, "status");
+  }
+  if (chain) bates_layout(A, s.bates, in.n, in.lp, 0, cus, o);
+  if (slab_bytes) s.slabs = A.take<char>(slab_bytes, "slabs");
+  return s;
+}
+
 // one score group of n candidates (groups: BG_SINE / BG_GAUSS / BG_DM; 0: pfe_params4, which
 // fits nothing).  A fit scores into a 22-column scratch d22 and hands out its k columns.
 // Inputs: the DM curves (BG_DM: lp = 0), the float profiles (f64) or the byte profiles, and

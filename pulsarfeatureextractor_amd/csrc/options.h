@@ -22,6 +22,8 @@ struct Options {
                                    // 2 chain splits only, 0 one lane per leaf
   int pfd_global = 0;              // PFD dmprof: 1 every shape on k_pfd_dmprof_g (the fold in global
                                    // scratch), 0 only the shapes that do not fit the LDS
+  int subf64_global = 0;           // float sub-bands: 1 every shape in per-wave slabs of global
+                                   // scratch, 0 only the shapes that do not fit the LDS
 };
 
 }  // namespace pfe

@@ -271,8 +271,17 @@ class PHCXOperations(ProfileOperations):
                                   np.asarray(scal, dtype=np.float64))
 
     def getSubbandParameters_batch(self, profiles, subbands, scal):
-        return self.engine.subband3(_u8_rows(profiles), np.asarray(subbands, dtype=np.uint8),
-                                    np.asarray(scal, dtype=np.float64))
+        """Byte-valued profiles and sub-bands (the rule of _profile_rows) go to pfe_subband3;
+        anything else (normalised or baseline-subtracted data) to pfe_subband3_f64."""
+        scal = np.asarray(scal, dtype=np.float64)
+        prof, pf = _profile_rows(profiles)
+        sub = np.asarray(subbands)
+        sf = sub.dtype != np.uint8 and bool(sub.size) and (
+            sub.min() < 0 or sub.max() > 255 or not np.array_equal(sub, np.round(sub)))
+        if pf or sf:
+            return self.engine.subband3_f64(np.ascontiguousarray(prof, dtype=np.float64),
+                                            np.ascontiguousarray(sub, dtype=np.float64), scal)
+        return self.engine.subband3(prof, sub.astype(np.uint8, copy=False), scal)
 
     def getCandidateParameters(self, data, section=None):
         """:81-112 -> [period (ms), snr, dm, width] as the method returns them (PHCXFile

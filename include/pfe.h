@@ -139,6 +139,9 @@ int pfe_synchronize(pfe_handle* h);
  *                        sub-bands fit the LDS stay on chip and every other shape goes through
  *                        per-wave slabs of the handle's scratch; 1 = every shape through the
  *                        slabs (same bits)
+ *   PFE_OPT_PFD_F32_CHUNK  the pfe_pfd_*_f32 calls: folds per pass, >= 0.  0 (default) = as many
+ *                        folds as keep a pass's part sums (nsub x proflen doubles a fold)
+ *                        within 1 GiB; a larger value is cut to that, and to n (same bits)
  * Returns PFE_EINVAL for an unknown option or an out-of-range value.
  * --------------------------------------------------------------------------------------- */
 #define PFE_OPT_SOLVER 1
@@ -153,6 +156,7 @@ int pfe_synchronize(pfe_handle* h);
 #define PFE_OPT_LYON8_DM_SPLIT 10
 #define PFE_OPT_PFD_GLOBAL 11
 #define PFE_OPT_SUBF64_GLOBAL 12
+#define PFE_OPT_PFD_F32_CHUNK 13
 #define PFE_SOLVER_POOLED 0
 #define PFE_SOLVER_BATCHED 1
 #define PFE_SOLVER_WAVE 2
@@ -413,6 +417,49 @@ int pfe_pfd_dmfit4(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* s
                    uint32_t flags);
 int pfe_pfd_subband3(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
                      uint32_t flags);
+
+/* ---- float32 folds: the five PFD calls on a cube of floats ----------------------------
+ * A fold that never was a .pfd file (PRESTO writes doubles) -- the output of a GPU folder, a
+ * float32 tensor -- is scored where it is: the cube is read once, as the 4-byte values it
+ * holds, and never widened in memory, on the host or on the device.
+ *
+ * Contract: the result of an _f32 call is, bit for bit, the result of the f64 call of the
+ * same name on the same cube widened value by value ((double)x, exact), with the same
+ * subfreqs and scal.  Nothing is accumulated in float32: every fold's parts are summed in
+ * fp64, S[e] = (double)X[0][e] + (double)X[1][e] + ... + (double)X[npart-1][e], in that order
+ * from the value of part 0 -- the order the f64 kernels sum the parts of an element in --
+ * and the f64 kernels run on S as folds of one part.  This is NOT numpy.sum of a float32
+ * array, which accumulates in float32: compare with profs.astype(numpy.float64) scored by the
+ * f64 call, or summed in fp64.  The header scalars (PFE_PFD_AVGPROF, PFE_PFD_VARPROF and the
+ * others) stay fp64 and stay the caller's to supply.
+ *
+ * Shape limits, PFE_EINVAL texts, status bits, stream behaviour, PFE_FLAG_DEVICE_PTRS and
+ * the routing options (PFE_OPT_PFD_WAVES, _SPLIT, _GLOBAL) are those of the f64 call of the
+ * same name; profs must be 4-byte aligned (16-byte aligned with nsub x proflen a multiple
+ * of 4 takes the 16-byte loads; same bits either way).
+ * Scratch: a call runs in passes of `chunk` folds -- chunk = min(n, max(1, 2^30 / (8 x nsub x
+ * proflen))), or PFE_OPT_PFD_F32_CHUNK when that is smaller -- and takes, behind the arrays a
+ * host-pointer call stages (the cube as n x npart x nsub x proflen floats: half the bytes of
+ * the f64 call over the bus), chunk x nsub x proflen doubles of part sums, then the scratch of
+ * the f64 call on `chunk` folds. */
+typedef struct pfe_pfd_f32_in {
+  const float* profs;     /* n x npart x nsub x proflen, dense, 4-byte aligned */
+  const double* subfreqs; /* n x nsub */
+  const double* scal;     /* n x PFE_PFD_NSCAL */
+  int32_t npart, nsub, proflen;
+  int64_t n;
+} pfe_pfd_f32_in;
+
+int pfe_pfd_dmprof_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* profile, float* chis,
+                       double* lyon8, uint32_t* status, uint32_t flags);
+int pfe_pfd_bates22_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uint32_t* status,
+                        uint32_t flags);
+int pfe_pfd_params4_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uint32_t* status,
+                        uint32_t flags);
+int pfe_pfd_dmfit4_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uint32_t* status,
+                       uint32_t flags);
+int pfe_pfd_subband3_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uint32_t* status,
+                         uint32_t flags);
 
 #ifdef __cplusplus
 }

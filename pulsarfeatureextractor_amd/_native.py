@@ -56,6 +56,11 @@ EXPORTED_SYMBOLS = (
     "pfe_pfd_params4",
     "pfe_pfd_dmfit4",
     "pfe_pfd_subband3",
+    "pfe_pfd_dmprof_f32",
+    "pfe_pfd_bates22_f32",
+    "pfe_pfd_params4_f32",
+    "pfe_pfd_dmfit4_f32",
+    "pfe_pfd_subband3_f32",
 )
 PFE_PFD_NSCAL = 8
 PFE_PFD_NDM = 100
@@ -89,6 +94,7 @@ OPTIONS = {
     "lyon8_dm_split": 10,  # 1 (default) chain splits + paired one-chunk rows, 2 splits only, 0 off
     "pfd_global": 11,   # 0 folds that fit stay in LDS (default), 1 every fold through global scratch
     "subf64_global": 12,  # float sub-bands: 0 shapes that fit stay in LDS (default), 1 all in scratch
+    "pfd_f32_chunk": 13,  # float32 folds: folds per pass (0, default: what 1 GiB of part sums holds)
 }
 SOLVERS = {"pooled": 0, "batched": 1, "wave": 2}
 
@@ -125,6 +131,10 @@ class PfdIn(C.Structure):
         ("proflen", C.c_int32),
         ("n", C.c_int64),
     ]
+
+
+class PfdF32In(PfdIn):
+    """pfe_pfd_f32_in: the fields of pfe_pfd_in, profs pointing at floats."""
 
 
 class PhcxInfo(C.Structure):
@@ -196,6 +206,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         lyon = [vp, vp, i64, i32, vp, i64, i32, i64, vp, vp, u32]
         bates = [vp, ptr(BatesIn), vp, vp, u32]
         pfd = [vp, ptr(PfdIn), vp, vp, u32]
+        pfd_f32 = [vp, ptr(PfdF32In), vp, vp, u32]
         f64 = [vp, vp, i32, i64, vp, vp, u32]
         bates_f64 = [vp, ptr(BatesF64In), vp, vp, u32]
         signatures = {  # name: (restype, argtypes), as include/pfe.h and include/pfe_io.h declare
@@ -214,6 +225,9 @@ def load_library(path: str | None = None) -> C.CDLL:
             "pfe_pfd_dmprof": (rc, [vp, ptr(PfdIn), vp, vp, vp, vp, u32]),
             "pfe_pfd_bates22": (rc, pfd), "pfe_pfd_params4": (rc, pfd),
             "pfe_pfd_dmfit4": (rc, pfd), "pfe_pfd_subband3": (rc, pfd),
+            "pfe_pfd_dmprof_f32": (rc, [vp, ptr(PfdF32In), vp, vp, vp, vp, u32]),
+            "pfe_pfd_bates22_f32": (rc, pfd_f32), "pfe_pfd_params4_f32": (rc, pfd_f32),
+            "pfe_pfd_dmfit4_f32": (rc, pfd_f32), "pfe_pfd_subband3_f32": (rc, pfd_f32),
             "pfe_phcx_parse": (rc, [ptr(C.c_char_p), i64, i32, i32, ptr(vp)]),
             "pfe_phcx_count": (i64, [vp]),
             "pfe_phcx_info_get": (rc, [vp, i64, ptr(PhcxInfo)]),
@@ -669,20 +683,30 @@ class Engine:
         if dev:
             import torch
 
-            self._dev(profs, "profs", (torch.float64,))
+            self._dev(profs, "profs", (torch.float64, torch.float32))
             self._dev(subfreqs, "subfreqs", (torch.float64,))
             self._dev(scal, "scal", (torch.float64,))
             self._follow_torch()
+            f32 = profs.dtype == torch.float32
         else:
-            profs = np.ascontiguousarray(profs, dtype=np.float64)
+            # a float32 cube goes to the _f32 call as it is: no copy, nothing widened
+            f32 = isinstance(profs, np.ndarray) and profs.dtype == np.float32
+            profs = np.ascontiguousarray(profs, dtype=np.float32 if f32 else np.float64)
             subfreqs = np.ascontiguousarray(subfreqs, dtype=np.float64)
             scal = np.ascontiguousarray(scal, dtype=np.float64)
-        pin = PfdIn(_ptr(profs), _ptr(subfreqs), _ptr(scal), npart, nsub, L, n)
+        pin = (PfdF32In if f32 else PfdIn)(_ptr(profs), _ptr(subfreqs), _ptr(scal), npart, nsub, L, n)
         return pin, dev, (profs, subfreqs, scal)
+
+    def _pfd_fn(self, fn, pin):
+        """The C entry point of a PFD call: its _f32 form for a float32 cube."""
+        return getattr(self.lib, "pfe_" + fn + ("_f32" if isinstance(pin, PfdF32In) else ""))
 
     def pfd_dmprof(self, profs, subfreqs, scal, profile=True, chis=True, lyon8=True):
         """PFD preprocessing + Lyon features (pfe_pfd_dmprof) for a batch of folds of one
         shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL).
+        A float32 cube (numpy array or device tensor) is scored as it is, by the _f32 call of
+        this and the other PFD methods: the bits of the f64 call on profs widened to f64
+        (parts summed in fp64; not numpy's float32 sum).  subfreqs and scal stay f64.
         Returns dict(profile (n,L) f64, chis (n,100) f32, lyon8 (n,8) f64, status (n,))."""
         pin, dev, keep = self._pfd_args(profs, subfreqs, scal, "pfd_dmprof")
         n, L = pin.n, pin.proflen
@@ -701,7 +725,7 @@ class Engine:
         out["chis"] = mk((n, PFE_PFD_NDM), f32) if chis else None
         out["lyon8"] = mk((n, 8), f64) if lyon8 else None
         out["status"] = mk((n,), i32)
-        self._check(self.lib.pfe_pfd_dmprof(
+        self._check(self._pfd_fn("pfd_dmprof", pin)(
             self._h, C.byref(pin), _ptr(out["profile"]) if profile else None,
             _ptr(out["chis"]) if chis else None, _ptr(out["lyon8"]) if lyon8 else None,
             _ptr(out["status"]), flags))
@@ -711,8 +735,7 @@ class Engine:
     def _pfd_scores(self, fn, k, profs, subfreqs, scal, out, status):
         pin, dev, keep = self._pfd_args(profs, subfreqs, scal, fn)
         out, status, flags = self._outputs(dev, profs, pin.n, k, out, status)
-        self._check(getattr(self.lib, "pfe_" + fn)(self._h, C.byref(pin), _ptr(out), _ptr(status),
-                                                   flags))
+        self._check(self._pfd_fn(fn, pin)(self._h, C.byref(pin), _ptr(out), _ptr(status), flags))
         del keep
         return out, status
 

@@ -325,6 +325,10 @@ int pfe_set_option(pfe_handle* h, int32_t option, int64_t v) {
       if (v != 0 && v != 1) break;
       o.subf64_global = (int)v;
       return PFE_OK;
+    case PFE_OPT_PFD_F32_CHUNK:
+      if (v < 0) break;
+      o.pfd_f32_chunk = v;
+      return PFE_OK;
     default:
       return set_err(h, PFE_EINVAL, "pfe_set_option: unknown option %d", option);
   }
@@ -348,6 +352,7 @@ int pfe_get_option(const pfe_handle* h, int32_t option, int64_t* v) {
     case PFE_OPT_LYON8_DM_SPLIT: *v = o.lyon8_dm_split; return PFE_OK;
     case PFE_OPT_PFD_GLOBAL: *v = o.pfd_global; return PFE_OK;
     case PFE_OPT_SUBF64_GLOBAL: *v = o.subf64_global; return PFE_OK;
+    case PFE_OPT_PFD_F32_CHUNK: *v = o.pfd_f32_chunk; return PFE_OK;
     default: return PFE_EINVAL;
   }
 }
@@ -862,41 +867,94 @@ static pfe::PfdArgs pfd_args(const pfe_handle* h, const pfe_pfd_in* in) {
   a.waves = h->opt.pfd_waves;
   return a;
 }
-// host path: the three inputs into their regions `d`, and `a` reads them there
-static int stage_pfd(pfe_handle* h, const pfe_pfd_in* in, const pfe::PfdInputs& d,
-                     pfe::PfdArgs& a) {
-  const size_t n = (size_t)in->n;
+// host path: the three inputs into their regions `d`, and `a` reads them there (x32: the
+// float cube of an _f32 call, copied as the floats it is; each pass points a.profs at its sums)
+static int stage_pfd(pfe_handle* h, const pfe_pfd_in* in, const float*& x32,
+                     const pfe::PfdInputs& d, pfe::PfdArgs& a) {
+  const size_t n = (size_t)in->n, cube = n * in->npart * in->nsub * in->proflen;
   int rc;
-  if ((rc = stage_in(h, d.profs, in->profs, n * in->npart * in->nsub * in->proflen)) ||
+  if ((rc = x32 ? stage_in(h, d.profs32, x32, cube) : stage_in(h, d.profs, in->profs, cube)) ||
       (rc = stage_in(h, d.subfreqs, in->subfreqs, n * in->nsub)) ||
       (rc = stage_in(h, d.scal, in->scal, n * PFE_PFD_NSCAL)))
     return rc;
-  a.profs = d.profs;
+  if (x32)
+    x32 = d.profs32;
+  else
+    a.profs = d.profs;
   a.subfreqs = d.subfreqs;
   a.scal = d.scal;
   return PFE_OK;
 }
 
-int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* chis,
-                   double* lyon8, uint32_t* status, uint32_t flags) {
+// The pfe_pfd_*_f32 calls go through the bodies of the f64 calls: `in` without its cube, the
+// float cube beside it
+struct PfdF32View {
+  pfe_pfd_in in{};
+  const float* x32 = nullptr;
+  const pfe_pfd_in* view = nullptr;  // null as the caller's `in` was
+  explicit PfdF32View(const pfe_pfd_f32_in* f) {
+    if (!f) return;
+    in.subfreqs = f->subfreqs;
+    in.scal = f->scal;
+    in.npart = f->npart;
+    in.nsub = f->nsub;
+    in.proflen = f->proflen;
+    in.n = f->n;
+    x32 = f->profs;
+    view = &in;
+  }
+};
+// a null or misaligned cube, in the words of the f64 call
+static int pfd_cube_check(pfe_handle* h, const char* fn, const pfe_pfd_in* in, bool f32,
+                          const float* x32) {
+  if ((f32 ? !x32 : !in->profs) || !in->subfreqs || !in->scal)
+    return set_err(h, PFE_EINVAL, "%s: null input array", fn);
+  if (f32 && ((uintptr_t)x32 & 3))
+    return set_err(h, PFE_EINVAL, "%s: profs not 4-byte aligned", fn);
+  return PFE_OK;
+}
+// Folds [c0, c0 + cn) of the batch `a`: the whole batch of an f64 call; one pass of a float32
+// call, whose part sums k_pfd_partsum_f32 forms in psum first, for the f64 kernels to read as
+// folds of one part.  Outputs are moved by the caller.
+static int pfd_pass(pfe_handle* h, const char* fn, const pfe::PfdArgs& a, const float* x32,
+                    double* psum, int64_t c0, int64_t cn, pfe::PfdArgs& b) {
+  b = a;
+  b.n = cn;
+  b.subfreqs = a.subfreqs + c0 * a.nsub;
+  b.scal = a.scal + c0 * PFE_PFD_NSCAL;
+  if (!x32) return PFE_OK;  // c0 = 0, cn = n
+  hipError_t e = pfe::launch_pfd_partsum_f32(x32 + c0 * a.npart * (int64_t)a.nsub * a.L, psum,
+                                             a.npart, a.nsub, a.L, cn, h->stream);
+  if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
+  b.profs = psum;
+  b.npart = 1;
+  return PFE_OK;
+}
+
+// pfe_pfd_dmprof, and pfe_pfd_dmprof_f32 (f32: the cube is x32, in->profs is not read)
+static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const float* x32,
+                           double* profile, float* chis, double* lyon8, uint32_t* status,
+                           uint32_t flags) {
   int64_t n;
   int rc = call_check(h, "pfd_dmprof", in, status != nullptr, n);
   if (rc || n == 0) return rc;
-  if (!in->profs || !in->subfreqs || !in->scal)
-    return set_err(h, PFE_EINVAL, "pfd_dmprof: null input array");
+  if ((rc = pfd_cube_check(h, "pfd_dmprof", in, f32, x32))) return rc;
   if (in->npart < 1 || in->nsub < 1 || in->proflen < 2)
     return set_err(h, PFE_EINVAL, "pfd_dmprof: shape %dx%dx%d", in->npart, in->nsub, in->proflen);
   const bool useg = pfd_use_global(h, in);
   if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
     return pfd_shape_err(h, "pfd_dmprof", in);
   if ((rc = call_begin(h))) return rc;
-  const pfe::PfdGlobalPlan gp = useg ? pfe::pfd_global_plan(in->nsub, in->proflen, n) : pfe::PfdGlobalPlan();
+  // folds per pass: all of them, or what the part sums of a float32 cube allow
+  const int64_t pass =
+      f32 ? pfe::pfd_f32_chunk(in->nsub, in->proflen, n, h->opt.pfd_f32_chunk) : n;
+  const pfe::PfdGlobalPlan gp = useg ? pfe::pfd_global_plan(in->nsub, in->proflen, pass) : pfe::PfdGlobalPlan();
   hipStream_t st = h->stream;
   pfe::PfdArgs a = pfd_args(h, in);
   // split pipeline: two buffers of part sums, chunks of up to 4096 folds
   // (2 x 4096 x nsub x L doubles: 268 MB at 32 x 128)
   const bool split = !useg && h->opt.pfd_split && h->fork.side[0] && pfe::pfd_split_ok(a);
-  const int64_t chunk = n < 4096 ? n : 4096;
+  const int64_t chunk = pass < 4096 ? pass : 4096;
   // (or the slabs of the global-memory kernel)
   const size_t ws_bytes =
       split ? 2 * (size_t)chunk * in->nsub * in->proflen * sizeof(double) : gp.bytes();
@@ -907,22 +965,32 @@ int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* 
   const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
   pfe::PfdDmprofStage s;
   rc = lay_out(h, s, [&](pfe::Arena& A) {
-    return pfe::pfd_dmprof_layout(A, *in, host, profile, chis, lyon8, ws_bytes);
+    return pfe::pfd_dmprof_layout(A, *in, host, profile, chis, lyon8, ws_bytes, f32 ? pass : 0);
   });
-  if (rc || (host && (rc = stage_pfd(h, in, s.in, a)))) return rc;
+  if (rc || (host && (rc = stage_pfd(h, in, x32, s.in, a)))) return rc;
   a.profile = host ? s.profile : profile;
   a.chis = host ? s.chis : chis;
   a.lyon8 = host ? s.lyon8 : lyon8;
   a.status = host ? s.status : status;
-  if (useg) {
-    a.tg = s.ws;
-    a.gblocks = gp.blocks;
-    a.gstride = gp.stride;
+  for (int64_t c0 = 0; c0 < n; c0 += pass) {
+    const int64_t cn = n - c0 < pass ? n - c0 : pass;
+    pfe::PfdArgs b;
+    if ((rc = pfd_pass(h, "pfd_dmprof", a, x32, s.in.psum, c0, cn, b))) return rc;
+    if (a.profile) b.profile = a.profile + c0 * a.L;
+    if (a.chis) b.chis = a.chis + c0 * PFE_PFD_NDM;
+    if (a.lyon8) b.lyon8 = a.lyon8 + c0 * 8;
+    b.status = a.status + c0;
+    if (useg) {
+      b.tg = s.ws;
+      b.gblocks = cn == pass ? gp.blocks : pfe::pfd_global_plan(in->nsub, in->proflen, cn).blocks;
+      b.gstride = gp.stride;
+    }
+    hipError_t e = split ? pfe::launch_pfd_dmprof_split(b, st, h->fork.side[0], (double*)s.ws,
+                                                        chunk, h->pev)
+                         : pfe::launch_pfd_dmprof(b, st);
+    if (e != hipSuccess)
+      return set_err(h, PFE_EDEVICE, "pfd_dmprof launch: %s", hipGetErrorString(e));
   }
-  hipError_t e = split ? pfe::launch_pfd_dmprof_split(a, st, h->fork.side[0], (double*)s.ws, chunk,
-                                                      h->pev)
-                       : pfe::launch_pfd_dmprof(a, st);
-  if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "pfd_dmprof launch: %s", hipGetErrorString(e));
   if (host) {
     if ((profile && (rc = fetch(h, profile, a.profile, (size_t)n * in->proflen))) ||
         (chis && (rc = fetch(h, chis, a.chis, (size_t)n * PFE_PFD_NDM))) ||
@@ -932,17 +1000,29 @@ int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* 
   return call_end(h);
 }
 
+int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* chis,
+                   double* lyon8, uint32_t* status, uint32_t flags) {
+  return pfd_dmprof_call(h, in, false, nullptr, profile, chis, lyon8, status, flags);
+}
+
+int pfe_pfd_dmprof_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* profile, float* chis,
+                       double* lyon8, uint32_t* status, uint32_t flags) {
+  const PfdF32View v(in);
+  return pfd_dmprof_call(h, v.view, true, v.x32, profile, chis, lyon8, status, flags);
+}
+
 }  // extern "C"
 
 // pfe_pfd_bates22 (groups = PFD_G_ALL: out n x 22) and the PFD group calls (one group: its k
-// columns from column c0 of the 22-score vector, or of the DM-fit inputs par22 when c0 < 0)
-static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
-                           uint32_t flags, const char* fn, unsigned groups, int c0, int k) {
+// columns from column c0 of the 22-score vector, or of the DM-fit inputs par22 when c0 < 0),
+// and their float32 forms (f32: the cube is x32, in->profs is not read)
+static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const float* x32,
+                           double* out, uint32_t* status, uint32_t flags, const char* fn,
+                           unsigned groups, int c0, int k) {
   int64_t n;
   int rc = call_check(h, fn, in, out && status, n);
   if (rc || n == 0) return rc;
-  if (!in->profs || !in->subfreqs || !in->scal)
-    return set_err(h, PFE_EINVAL, "%s: null input array", fn);
+  if ((rc = pfd_cube_check(h, fn, in, f32, x32))) return rc;
   if (in->npart < 1 || in->nsub < 2 || in->proflen < 8 || in->proflen > 1024)
     return set_err(h, PFE_EINVAL, "%s: shape %dx%dx%d unsupported", fn, in->npart, in->nsub,
                    in->proflen);
@@ -950,59 +1030,120 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, double* out, uin
   if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
     return pfd_shape_err(h, fn, in);
   if ((rc = call_begin(h))) return rc;
-  const pfe::PfdGlobalPlan gp = useg ? pfe::pfd_global_plan(in->nsub, in->proflen, n) : pfe::PfdGlobalPlan();
+  // folds per pass: all of them, or what the part sums of a float32 cube allow
+  const int64_t pass =
+      f32 ? pfe::pfd_f32_chunk(in->nsub, in->proflen, n, h->opt.pfd_f32_chunk) : n;
+  auto plan = [&](int64_t cn) {
+    return useg ? pfe::pfd_global_plan(in->nsub, in->proflen, cn) : pfe::PfdGlobalPlan();
+  };
   hipStream_t st = h->stream;
   pfe::PfdArgs a = pfd_args(h, in);
   const bool all = groups == pfe::PFD_G_ALL;
   const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
   const int cus = pfe::device_cus();
+  // the scratch with the chain's workspace laid out for a pass of cn folds
+  auto walk = [&](int64_t cn) {
+    return [&, cn](pfe::Arena& A) {
+      return pfe::pfd_scores_layout(A, *in, host, groups, k, plan(cn).bytes(), cus, h->opt,
+                                    f32 ? pass : 0, cn);
+    };
+  };
+  if (n % pass) {  // a shorter last pass: its layout fits as well
+    pfe::Arena last;
+    walk(n % pass)(last);
+    if ((rc = ensure_scratch(h, last.bytes()))) return rc;
+  }
   pfe::PfdScoresStage s;
-  rc = lay_out(h, s, [&](pfe::Arena& A) {
-    return pfe::pfd_scores_layout(A, *in, host, groups, k, gp.bytes(), cus, h->opt);
-  });
-  if (rc || (host && (rc = stage_pfd(h, in, s.in, a)))) return rc;
+  rc = lay_out(h, s, walk(pass));
+  if (rc || (host && (rc = stage_pfd(h, in, x32, s.in, a)))) return rc;
   double* dout = host ? s.out : out;
   uint32_t* dstat = host ? s.status : status;
-  double* d22 = all ? dout : s.d22;  // a group call scores into a 22-column scratch of its own
-  if (useg) {
-    a.tg = s.tg;
-    a.gblocks = gp.blocks;
-    a.gstride = gp.stride;
-  }
-  hipError_t e = pfe::launch_pfd22(a, d22, dstat, s.work, st, &h->fork, h->opt, groups, !all);
-  if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
-  if (!all) {
-    hipLaunchKernelGGL(k_take_cols, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st,
-                       c0 < 0 ? s.work.par22 : d22, c0 < 0 ? 8 : 22, c0 < 0 ? 0 : c0, k, n, dout);
-    PFE_HIP(h, hipGetLastError());
+  for (int64_t f0 = 0; f0 < n; f0 += pass) {
+    const int64_t cn = n - f0 < pass ? n - f0 : pass;
+    if (cn != pass) {
+      pfe::Arena place{(uintptr_t)h->scratch};
+      s = walk(cn)(place);
+    }
+    pfe::PfdArgs b;
+    if ((rc = pfd_pass(h, fn, a, x32, s.in.psum, f0, cn, b))) return rc;
+    // a group call scores into a 22-column scratch of its own
+    double* d22 = all ? dout + f0 * 22 : s.d22;
+    if (useg) {
+      const pfe::PfdGlobalPlan gp = plan(cn);
+      b.tg = s.tg;
+      b.gblocks = gp.blocks;
+      b.gstride = gp.stride;
+    }
+    hipError_t e =
+        pfe::launch_pfd22(b, d22, dstat + f0, s.work, st, &h->fork, h->opt, groups, !all);
+    if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
+    if (!all) {
+      hipLaunchKernelGGL(k_take_cols, dim3((unsigned)((cn * k + 255) / 256)), dim3(256), 0, st,
+                         c0 < 0 ? s.work.par22 : d22, c0 < 0 ? 8 : 22, c0 < 0 ? 0 : c0, k, cn,
+                         dout + f0 * k);
+      PFE_HIP(h, hipGetLastError());
+    }
   }
   if (host && (rc = fetch_out(h, out, dout, k, status, dstat, n))) return rc;
   return call_end(h);
+}
+
+// what each of the four score calls asks of pfd_scores_call
+struct PfdScores {
+  const char* fn;
+  unsigned groups;
+  int c0, k;
+};
+static constexpr PfdScores PFD_BATES22{"pfd_bates22", pfe::PFD_G_ALL, 0, 22};
+// [period_ms, snr, dm, width] as getCandidateParameters returns them: par22's first columns
+static constexpr PfdScores PFD_PARAMS4{"pfd_params4", pfe::PFD_G_PARAMS, -1, 4};
+static constexpr PfdScores PFD_DMFIT4{"pfd_dmfit4", pfe::PFD_G_PARAMS | pfe::PFD_G_DM, 15, 4};
+static constexpr PfdScores PFD_SUBBAND3{"pfd_subband3", pfe::PFD_G_PARAMS | pfe::PFD_G_SUB, 19, 3};
+
+static int pfd_scores_f64(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
+                          uint32_t flags, const PfdScores& c) {
+  return pfd_scores_call(h, in, false, nullptr, out, status, flags, c.fn, c.groups, c.c0, c.k);
+}
+static int pfd_scores_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uint32_t* status,
+                          uint32_t flags, const PfdScores& c) {
+  const PfdF32View v(in);
+  return pfd_scores_call(h, v.view, true, v.x32, out, status, flags, c.fn, c.groups, c.c0, c.k);
 }
 
 extern "C" {
 
 int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
                     uint32_t flags) {
-  return pfd_scores_call(h, in, out, status, flags, "pfd_bates22", pfe::PFD_G_ALL, 0, 22);
+  return pfd_scores_f64(h, in, out, status, flags, PFD_BATES22);
 }
-
-// [period_ms, snr, dm, width] as getCandidateParameters returns them: par22's first columns
 int pfe_pfd_params4(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
                     uint32_t flags) {
-  return pfd_scores_call(h, in, out, status, flags, "pfd_params4", pfe::PFD_G_PARAMS, -1, 4);
+  return pfd_scores_f64(h, in, out, status, flags, PFD_PARAMS4);
 }
-
 int pfe_pfd_dmfit4(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
                    uint32_t flags) {
-  return pfd_scores_call(h, in, out, status, flags, "pfd_dmfit4",
-                         pfe::PFD_G_PARAMS | pfe::PFD_G_DM, 15, 4);
+  return pfd_scores_f64(h, in, out, status, flags, PFD_DMFIT4);
 }
-
 int pfe_pfd_subband3(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
                      uint32_t flags) {
-  return pfd_scores_call(h, in, out, status, flags, "pfd_subband3",
-                         pfe::PFD_G_PARAMS | pfe::PFD_G_SUB, 19, 3);
+  return pfd_scores_f64(h, in, out, status, flags, PFD_SUBBAND3);
+}
+
+int pfe_pfd_bates22_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uint32_t* status,
+                        uint32_t flags) {
+  return pfd_scores_f32(h, in, out, status, flags, PFD_BATES22);
+}
+int pfe_pfd_params4_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uint32_t* status,
+                        uint32_t flags) {
+  return pfd_scores_f32(h, in, out, status, flags, PFD_PARAMS4);
+}
+int pfe_pfd_dmfit4_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uint32_t* status,
+                       uint32_t flags) {
+  return pfd_scores_f32(h, in, out, status, flags, PFD_DMFIT4);
+}
+int pfe_pfd_subband3_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uint32_t* status,
+                         uint32_t flags) {
+  return pfd_scores_f32(h, in, out, status, flags, PFD_SUBBAND3);
 }
 
 }  // extern "C"

@@ -279,21 +279,49 @@ inline GroupStage group_layout(Arena& A, int64_t n_, int lp, int ndm, unsigned g
   return s;
 }
 
-// the three inputs every PFD call stages
+// ---- float32 fold cubes: the pfe_pfd_*_f32 calls (pfd_f32.hip) ---------------------------
+// A float32 call runs in passes of `chunk` folds: k_pfd_partsum_f32 sums the parts of the
+// pass's folds into psum (chunk x nsub x proflen doubles), and the f64 kernels run on psum
+// with npart = 1.  chunk: as many folds as keep psum within 1 GiB (at least one), fewer when
+// PFE_OPT_PFD_F32_CHUNK (opt > 0) asks for fewer, never more than n.
+constexpr size_t PFD_F32_PSUM_BUDGET = (size_t)1 << 30;
+inline int64_t pfd_f32_chunk(int nsub, int L, int64_t n, int64_t opt) {
+  int64_t c = (int64_t)(PFD_F32_PSUM_BUDGET / ((size_t)nsub * (size_t)L * sizeof(double)));
+  if (c < 1) c = 1;
+  if (opt > 0 && opt < c) c = opt;
+  return c < n ? c : n;
+}
+// s[c][e] = (double)x[c][0][e] + ... + (double)x[c][npart-1][e], e over nsub x L, c over n folds
+hipError_t launch_pfd_partsum_f32(const float* x, double* s, int npart, int nsub, int L, int64_t n,
+                                  hipStream_t st);
+
+// the three inputs every PFD call stages.  A float32 call (f32_chunk > 0: its folds per pass)
+// stages the cube as the floats it is (profs32, no profs), and -- host pointers or device --
+// takes psum behind its staged arrays
 struct PfdInputs {
   double *profs = nullptr, *subfreqs = nullptr, *scal = nullptr;
+  float* profs32 = nullptr;
+  double* psum = nullptr;
 };
-inline PfdInputs pfd_inputs_layout(Arena& A, const pfe_pfd_in& in) {
+inline PfdInputs pfd_inputs_layout(Arena& A, const pfe_pfd_in& in, bool f32 = false) {
   PfdInputs s;
-  const size_t n = (size_t)in.n;
-  s.profs = A.take<double>(n * in.npart * in.nsub * in.proflen, "profs");
+  const size_t n = (size_t)in.n, cube = n * in.npart * in.nsub * in.proflen;
+  if (f32)
+    s.profs32 = A.take<float>(cube, "profs32");
+  else
+    s.profs = A.take<double>(cube, "profs");
   s.subfreqs = A.take<double>(n * in.nsub, "subfreqs");
   s.scal = A.take<double>(n * PFE_PFD_NSCAL, "scal");
   return s;
 }
+inline double* pfd_psum_layout(Arena& A, const pfe_pfd_in& in, int64_t f32_chunk) {
+  return A.take<double>((size_t)f32_chunk * in.nsub * in.proflen, "psum");
+}
 
 // pfe_pfd_dmprof: the outputs the caller asked for, then ws_bytes for the two part-sum
-// buffers of the split pipeline or the slabs of the global-memory kernel (PfdGlobalPlan)
+// buffers of the split pipeline or the slabs of the global-memory kernel (PfdGlobalPlan).
+// pfe_pfd_dmprof_f32 (f32_chunk > 0): the same with the float cube and psum; ws_bytes is
+// then what one pass needs
 struct PfdDmprofStage {
   PfdInputs in;
   double* profile = nullptr;
@@ -303,23 +331,28 @@ struct PfdDmprofStage {
   void* ws = nullptr;
 };
 inline PfdDmprofStage pfd_dmprof_layout(Arena& A, const pfe_pfd_in& in, bool host, bool profile,
-                                        bool chis, bool lyon8, size_t ws_bytes) {
+                                        bool chis, bool lyon8, size_t ws_bytes,
+                                        int64_t f32_chunk = 0) {
   PfdDmprofStage s;
   const size_t n = (size_t)in.n;
   if (host) {
-    s.in = pfd_inputs_layout(A, in);
+    s.in = pfd_inputs_layout(A, in, f32_chunk > 0);
     if (profile) s.profile = A.take<double>(n * in.proflen, "profile");
     if (chis) s.chis = A.take<float>(n * PFE_PFD_NDM, "chis");
     if (lyon8) s.lyon8 = A.take<double>(n * 8, "lyon8");
     s.status = A.take<uint32_t>(n, "status");
   }
+  if (f32_chunk > 0) s.in.psum = pfd_psum_layout(A, in, f32_chunk);
   if (ws_bytes) s.ws = A.take<char>(ws_bytes, "ws");
   return s;
 }
 
 // pfe_pfd_bates22 (groups = PFD_G_ALL, k = 22) and the PFD group calls, which score into a
 // 22-column scratch d22 of their own and hand out k columns; g_bytes: the slabs of the
-// global-memory kernel (0: the fold lives in LDS)
+// global-memory kernel (0: the fold lives in LDS).  The float32 forms (f32_chunk > 0): the
+// float cube and psum, and d22, the chain's workspace and g_bytes for the `pass` folds of one
+// pass (a pass's chain then works on what the f64 call on that many folds lays out); the
+// staged arrays and psum come first, so they stay put from one pass to the next
 struct PfdScoresStage {
   PfdInputs in;
   double *out = nullptr, *d22 = nullptr;
@@ -329,16 +362,19 @@ struct PfdScoresStage {
 };
 inline PfdScoresStage pfd_scores_layout(Arena& A, const pfe_pfd_in& in, bool host,
                                         unsigned groups, int k, size_t g_bytes, int cus,
-                                        const Options& o) {
+                                        const Options& o, int64_t f32_chunk = 0,
+                                        int64_t pass = 0) {
   PfdScoresStage s;
   const size_t n = (size_t)in.n;
+  const int64_t wn = f32_chunk > 0 ? pass : in.n;
   if (host) {
-    s.in = pfd_inputs_layout(A, in);
+    s.in = pfd_inputs_layout(A, in, f32_chunk > 0);
     s.out = A.take<double>(n * k, "out");
     s.status = A.take<uint32_t>(n, "status");
   }
-  if (groups != PFD_G_ALL) s.d22 = A.take<double>(n * 22, "d22");
-  s.work = pfd22_layout(A, in.n, in.proflen, groups, cus, o);
+  if (f32_chunk > 0) s.in.psum = pfd_psum_layout(A, in, f32_chunk);
+  if (groups != PFD_G_ALL) s.d22 = A.take<double>((size_t)wn * 22, "d22");
+  s.work = pfd22_layout(A, wn, in.proflen, groups, cus, o);
   if (g_bytes) s.tg = A.take<char>(g_bytes, "tg");
   return s;
 }

@@ -24,6 +24,8 @@ struct Options {
                                    // scratch), 0 only the shapes that do not fit the LDS
   int subf64_global = 0;           // float sub-bands: 1 every shape in per-wave slabs of global
                                    // scratch, 0 only the shapes that do not fit the LDS
+  int64_t pfd_f32_chunk = 0;       // float32 folds: folds per pass (0: as many as 1 GiB of part
+                                   // sums holds)
 };
 
 }  // namespace pfe

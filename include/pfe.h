@@ -15,6 +15,8 @@
  *   pfe_lyon8_f64  <- the same two functions on float profiles (PFDFile.py:522-583)
  *   pfe_bates22    <- PHCXFile.compute                            PHCXFile.py:383-409
  *                     (score groups 1-4 :413, 5-11 :475, 12-15 :547, 16-19 :589, 20-22 :633)
+ *   Every call that takes float arrays has an _f64 form (doubles) and an _f32 form (floats read
+ *   where they lie, the bits of the _f64 form on the widened values): see the end of this file.
  *
  * Conventions
  *   - One handle per (device, stream).  Calls on one handle are serialised by the caller;
@@ -460,6 +462,73 @@ int pfe_pfd_dmfit4_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uin
                        uint32_t flags);
 int pfe_pfd_subband3_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uint32_t* status,
                          uint32_t flags);
+
+/* ---- float32 candidates: the float-array calls on arrays of floats ----------------------
+ * A candidate that never was a .pfd or .phcx file -- a float32 tensor from a GPU folder or a
+ * normalising step, the arrays an ML pipeline keeps, the float32 DM curve pfe_pfd_dmprof
+ * returns in `chis` -- is scored where it is: every float array the f64 calls take as doubles
+ * is taken here as 4-byte floats and read as such.
+ *
+ * Contract: the result of an _f32 call is, bit for bit, the result of the _f64 call of the same
+ * name on the same arrays widened value by value ((double)x, exact; float32 subnormals, signed
+ * zeros, infinities and NaNs are carried), in every column it returns (skew included: the same
+ * device pow on the same value), in the placement of NaNs and in the status bits.  Nothing is
+ * computed in float32: each value is widened at its load and every operation is the fp64
+ * operation of the f64 call, in its order.  This is NOT numpy on a float32 array, which
+ * accumulates in float32 (numpy.mean, numpy.sum, numpy.corrcoef of float32 rows): compare with
+ * the f64 call on x.astype(numpy.float64).
+ *
+ * Shape limits, PFE_EINVAL texts (under the _f32 name), status bits, stream behaviour,
+ * PFE_FLAG_DEVICE_PTRS and the options (PFE_OPT_SOLVER, _SERIAL, _HANDOVER, _GSLOTS,
+ * _SUBF64_GLOBAL, PFE_OPT_LYON8_BLOCKS) are those of the f64 call of the same name.  Float
+ * arrays must be 4-byte aligned (any such alignment gives the same bits; a sub-band array whose
+ * candidates start on 16-byte boundaries takes 16-byte loads throughout); scal and out keep the
+ * 8 bytes of the f64 calls.  Dense rows, except pfe_lyon8_f32, which takes any row strides that
+ * are at least the row lengths, in floats.  Inputs are never written.
+ *
+ *   pfe_lyon8_f32      the kernels of pfe_lyon8_f64 loading floats: both passes (the sum, then
+ *                      the powers of x - mean) add in numpy's float64 order.  Host rows cross
+ *                      the bus as floats, chunked and overlapped as for pfe_lyon8_f64.
+ *   pfe_sinusoid4_f32, pfe_gauss7_f32
+ *                      the profiles are widened once into the handle's scratch and the fit
+ *                      kernels of the f64 calls run on that copy.
+ *   pfe_subband3_f32   a candidate's nsub x lsb floats are widened on their way into the copy
+ *                      the f64 call makes of them (LDS partition or scratch slab, still
+ *                      doubles: the LDS budget and the on-chip / slab routing are unchanged),
+ *                      and its profile row likewise.
+ *   pfe_bates22_f32    the profiles and the DM curves are widened into the scratch on the
+ *                      handle's stream, then the groups run as in pfe_bates22_f64 (side
+ *                      streams, joined before the call returns) with the sub-band kernel of
+ *                      pfe_subband3_f32.  dmcurve may be the `chis` of pfe_pfd_dmprof.
+ * Scratch: that of the f64 call of the same name, plus n x lp doubles (pfe_sinusoid4_f32,
+ * pfe_gauss7_f32, pfe_bates22_f32) and n x ndm doubles (pfe_bates22_f32) for the widened
+ * copies; on the host path the staged arrays are floats instead of doubles (half the bytes
+ * over the bus).  The sub-bands are never widened in memory; pfe_subband3_f32 and
+ * pfe_lyon8_f32 take no scratch beyond the f64 call's. */
+int pfe_lyon8_f32(pfe_handle* h, const float* prof, int64_t prof_stride, int32_t lp,
+                  const float* dm, int64_t dm_stride, int32_t ld, int64_t n, double* out,
+                  uint32_t* status, uint32_t flags);
+int pfe_sinusoid4_f32(pfe_handle* h, const float* prof, int32_t lp, int64_t n, double* out,
+                      uint32_t* status, uint32_t flags);
+int pfe_gauss7_f32(pfe_handle* h, const float* prof, int32_t lp, int64_t n, double* out,
+                   uint32_t* status, uint32_t flags);
+
+typedef struct pfe_bates_f32_in {
+  const float* prof;     /* n x lp */
+  int32_t lp;
+  const float* sub;      /* n x nsub x lsb */
+  int32_t nsub;
+  int32_t lsb;
+  const float* dmcurve;  /* n x ndm */
+  int32_t ndm;
+  const double* scal;    /* n x PFE_NSCAL, fp64 as everywhere */
+  int64_t n;
+} pfe_bates_f32_in;
+
+int pfe_subband3_f32(pfe_handle* h, const pfe_bates_f32_in* in, double* out, uint32_t* status,
+                     uint32_t flags);
+int pfe_bates22_f32(pfe_handle* h, const pfe_bates_f32_in* in, double* out, uint32_t* status,
+                    uint32_t flags);
 
 #ifdef __cplusplus
 }

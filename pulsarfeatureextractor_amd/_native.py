@@ -61,6 +61,11 @@ EXPORTED_SYMBOLS = (
     "pfe_pfd_params4_f32",
     "pfe_pfd_dmfit4_f32",
     "pfe_pfd_subband3_f32",
+    "pfe_lyon8_f32",
+    "pfe_sinusoid4_f32",
+    "pfe_gauss7_f32",
+    "pfe_subband3_f32",
+    "pfe_bates22_f32",
 )
 PFE_PFD_NSCAL = 8
 PFE_PFD_NDM = 100
@@ -119,6 +124,10 @@ class BatesIn(C.Structure):
 
 class BatesF64In(BatesIn):
     """pfe_bates_f64_in: the fields of pfe_bates_in, prof and sub pointing at doubles."""
+
+
+class BatesF32In(BatesIn):
+    """pfe_bates_f32_in: the fields of pfe_bates_in, prof, sub and dmcurve pointing at floats."""
 
 
 class PfdIn(C.Structure):
@@ -209,6 +218,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         pfd_f32 = [vp, ptr(PfdF32In), vp, vp, u32]
         f64 = [vp, vp, i32, i64, vp, vp, u32]
         bates_f64 = [vp, ptr(BatesF64In), vp, vp, u32]
+        bates_f32 = [vp, ptr(BatesF32In), vp, vp, u32]
         signatures = {  # name: (restype, argtypes), as include/pfe.h and include/pfe_io.h declare
             "pfe_abi_version": (rc, []), "pfe_device_count": (rc, []),
             "pfe_create": (rc, [C.c_int, ptr(vp)]), "pfe_destroy": (None, [vp]),
@@ -228,6 +238,9 @@ def load_library(path: str | None = None) -> C.CDLL:
             "pfe_pfd_dmprof_f32": (rc, [vp, ptr(PfdF32In), vp, vp, vp, vp, u32]),
             "pfe_pfd_bates22_f32": (rc, pfd_f32), "pfe_pfd_params4_f32": (rc, pfd_f32),
             "pfe_pfd_dmfit4_f32": (rc, pfd_f32), "pfe_pfd_subband3_f32": (rc, pfd_f32),
+            "pfe_lyon8_f32": (rc, lyon),
+            "pfe_sinusoid4_f32": (rc, f64), "pfe_gauss7_f32": (rc, f64),
+            "pfe_subband3_f32": (rc, bates_f32), "pfe_bates22_f32": (rc, bates_f32),
             "pfe_phcx_parse": (rc, [ptr(C.c_char_p), i64, i32, i32, ptr(vp)]),
             "pfe_phcx_count": (i64, [vp]),
             "pfe_phcx_info_get": (rc, [vp, i64, ptr(PhcxInfo)]),
@@ -442,7 +455,10 @@ class Engine:
 
     # -- 8 Lyon features -----------------------------------------------------------------
     def lyon8(self, prof, dm, out=None, status=None):
-        """[mean,std,skew,kurt] of each profile row then each DM row -> (n, 8) float64."""
+        """[mean,std,skew,kurt] of each profile row then each DM row -> (n, 8) float64.
+        Rows are uint8, float64 or float32 (both arrays the same): float32 rows go to
+        pfe_lyon8_f32 as they are and give the bits of the float64 call on the widened rows
+        (every sum in fp64; not numpy's float32 mean)."""
         if prof.ndim != 2 or dm.ndim != 2 or prof.shape[0] != dm.shape[0]:
             raise ValueError("prof and dm must be 2-D with the same number of rows")
         n = prof.shape[0]
@@ -452,9 +468,9 @@ class Engine:
         if dev:
             import torch
 
-            self._dev(prof, "prof", (torch.uint8, torch.float64), rows_contig=True)
+            self._dev(prof, "prof", (torch.uint8, torch.float64, torch.float32), rows_contig=True)
             self._dev(dm, "dm", (prof.dtype,), rows_contig=True)
-            kind = "u8" if prof.dtype == torch.uint8 else "f64"
+            kind = {torch.uint8: "u8", torch.float64: "f64", torch.float32: "f32"}[prof.dtype]
             self._follow_torch()
             ps, ds = _row_stride(prof.stride(0), prof), _row_stride(dm.stride(0), dm)
         else:
@@ -462,14 +478,16 @@ class Engine:
                 kind = "u8"
             elif prof.dtype == np.float64 and dm.dtype == np.float64:
                 kind = "f64"
+            elif prof.dtype == np.float32 and dm.dtype == np.float32:
+                kind = "f32"
             else:
-                raise TypeError("lyon8: rows must be uint8 or float64 (same dtype)")
+                raise TypeError("lyon8: rows must be uint8, float64 or float32 (same dtype)")
             prof = prof if prof.strides[1] == prof.itemsize else np.ascontiguousarray(prof)
             dm = dm if dm.strides[1] == dm.itemsize else np.ascontiguousarray(dm)
             ps = _row_stride(prof.strides[0] // prof.itemsize, prof)
             ds = _row_stride(dm.strides[0] // dm.itemsize, dm)
         out, status, flags = self._outputs(dev, prof, n, 8, out, status, need_status=False)
-        fn = self.lib.pfe_lyon8_u8 if kind == "u8" else self.lib.pfe_lyon8_f64
+        fn = getattr(self.lib, "pfe_lyon8_" + kind)
         st = None if status is None else _ptr(status)
         self._check(
             fn(self._h, _ptr(prof), ps, prof.shape[1], _ptr(dm), ds, dm.shape[1], n,
@@ -568,7 +586,7 @@ class Engine:
         """getDMFittings (pfe_dmfit4): [peak, |1 - Prop|, Shift (signed), chi_theo]."""
         return self._group("pfe_dmfit4", 4, None, dmcurve, scal, out, status)
 
-    def _group_f64(self, fn, k, prof, out, status):
+    def _group_f64(self, fn, k, prof, out, status, bits=64):
         if prof.ndim != 2:
             raise ValueError("prof must be (n, lp)")
         n, lp = prof.shape
@@ -576,11 +594,11 @@ class Engine:
         if dev:
             import torch
 
-            self._dev(prof, "prof", (torch.float64,))
+            self._dev(prof, "prof", (torch.float64 if bits == 64 else torch.float32,))
             self._follow_torch()
         else:
-            if not isinstance(prof, np.ndarray) or prof.dtype != np.float64:
-                raise TypeError(f"{fn}: float64 profile rows expected (byte profiles go through "
+            if not isinstance(prof, np.ndarray) or prof.dtype != np.dtype(f"float{bits}"):
+                raise TypeError(f"{fn}: float{bits} profile rows expected (byte profiles go through "
                                 "sinusoid4 / gauss7)")
             prof = np.ascontiguousarray(prof)
         out, status, flags = self._outputs(dev, prof, n, k, out, status)
@@ -597,8 +615,17 @@ class Engine:
         """getGaussianFittings on float profiles (pfe_gauss7_f64) -> ((n, 7) s5-s11, status)."""
         return self._group_f64("pfe_gauss7_f64", 7, prof, out, status)
 
-    # ---- candidates held as float arrays (pfe.h pfe_bates_f64_in) ------------------------
-    def _bates_f64_args(self, fn, prof, sub, dmcurve, scal, with_dm):
+    def sinusoid4_f32(self, prof, out=None, status=None):
+        """sinusoid4_f64 on float32 profiles (pfe_sinusoid4_f32): the bits of sinusoid4_f64 on
+        the widened rows -> ((n, 4) s1-s4, (n,) status)."""
+        return self._group_f64("pfe_sinusoid4_f32", 4, prof, out, status, bits=32)
+
+    def gauss7_f32(self, prof, out=None, status=None):
+        """gauss7_f64 on float32 profiles (pfe_gauss7_f32) -> ((n, 7) s5-s11, status)."""
+        return self._group_f64("pfe_gauss7_f32", 7, prof, out, status, bits=32)
+
+    # ---- candidates held as float arrays (pfe.h pfe_bates_f64_in, pfe_bates_f32_in) --------
+    def _bates_f64_args(self, fn, prof, sub, dmcurve, scal, with_dm, bits=64):
         if prof.ndim != 2 or sub.ndim != 3 or scal.ndim != 2 or scal.shape[1] != PFE_NSCAL:
             raise ValueError("prof must be (n,lp), sub (n,nsub,lsb), scal (n,%d)" % PFE_NSCAL)
         n = prof.shape[0]
@@ -611,10 +638,11 @@ class Engine:
         if dev:
             import torch
 
+            ft = torch.float64 if bits == 64 else torch.float32
             for nm, a in arrays:  # dense rows only: a strided tensor is refused, never copied
-                self._dev(a, nm, (torch.float64,))
+                self._dev(a, nm, (torch.float64 if nm == "scal" else ft,))
             self._follow_torch()
-        else:
+        elif bits == 64:
             for nm, a in arrays:
                 if not isinstance(a, np.ndarray) or (nm in ("prof", "sub") and a.dtype != np.float64):
                     raise TypeError(f"{fn}: {nm}: float64 numpy rows expected (byte candidates go "
@@ -622,7 +650,16 @@ class Engine:
             prof, sub, scal = (np.ascontiguousarray(a, dtype=np.float64) for a in (prof, sub, scal))
             if with_dm:
                 dmcurve = np.ascontiguousarray(dmcurve, dtype=np.float64)
-        bi = BatesF64In(
+        else:
+            for nm, a in arrays:  # nothing is converted: a float32 call reads what it is given
+                want = np.float64 if nm == "scal" else np.float32
+                if not isinstance(a, np.ndarray) or a.dtype != want:
+                    raise TypeError(f"{fn}: {nm}: {np.dtype(want).name} numpy rows expected "
+                                    "(float64 candidates go through subband3_f64 / bates22_f64)")
+            prof, sub, scal = (np.ascontiguousarray(a) for a in (prof, sub, scal))
+            if with_dm:
+                dmcurve = np.ascontiguousarray(dmcurve)
+        bi = (BatesF64In if bits == 64 else BatesF32In)(
             _ptr(prof), prof.shape[1], _ptr(sub), sub.shape[1], sub.shape[2],
             _ptr(dmcurve) if with_dm else None, dmcurve.shape[1] if with_dm else 0,
             _ptr(scal), n,
@@ -647,6 +684,26 @@ class Engine:
         bi, dev, keep = self._bates_f64_args("bates22_f64", prof, sub, dmcurve, scal, True)
         out, status, flags = self._outputs(dev, keep[0], bi.n, 22, out, status)
         self._check(self.lib.pfe_bates22_f64(self._h, C.byref(bi), _ptr(out), _ptr(status), flags))
+        del keep
+        return out, status
+
+    def subband3_f32(self, prof, sub, scal, out=None, status=None):
+        """subband3_f64 on float32 arrays (pfe_subband3_f32): prof (n, lp) and sub (n, nsub, lsb)
+        float32, scal (n, 8) float64 -> ((n, 3) float64, (n,) status), the bits of subband3_f64
+        on the widened arrays.  The sub-bands are read where they lie and never written."""
+        bi, dev, keep = self._bates_f64_args("subband3_f32", prof, sub, None, scal, False, bits=32)
+        out, status, flags = self._outputs(dev, keep[0], bi.n, 3, out, status)
+        self._check(self.lib.pfe_subband3_f32(self._h, C.byref(bi), _ptr(out), _ptr(status), flags))
+        del keep
+        return out, status
+
+    def bates22_f32(self, prof, sub, dmcurve, scal, out=None, status=None):
+        """bates22_f64 on float32 arrays (pfe_bates22_f32): prof, sub and dmcurve float32 (the
+        curve may be pfd_dmprof's chis), scal float64 -> ((n, 22) float64, (n,) status), the
+        bits of bates22_f64 on the widened arrays."""
+        bi, dev, keep = self._bates_f64_args("bates22_f32", prof, sub, dmcurve, scal, True, bits=32)
+        out, status, flags = self._outputs(dev, keep[0], bi.n, 22, out, status)
+        self._check(self.lib.pfe_bates22_f32(self._h, C.byref(bi), _ptr(out), _ptr(status), flags))
         del keep
         return out, status
 

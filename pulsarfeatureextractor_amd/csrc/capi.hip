@@ -13,6 +13,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 
 #include "../../include/pfe.h"
 #include "launch.h"
@@ -382,6 +383,9 @@ static hipError_t launch_lyon8(const T* prof, int64_t ps, int lp, const T* dm, i
   if constexpr (sizeof(T) == 1)
     return pfe::launch_lyon8_u8((const uint8_t*)prof, ps, lp, (const uint8_t*)dm, ds, ld, n, out,
                                 st, o);
+  else if constexpr (sizeof(T) == 4)
+    return pfe::launch_lyon8_f32((const float*)prof, ps, lp, (const float*)dm, ds, ld, n, out, st,
+                                 o);
   else
     return pfe::launch_lyon8_f64((const double*)prof, ps, lp, (const double*)dm, ds, ld, n, out,
                                  st, o);
@@ -509,6 +513,8 @@ static int lyon8_impl(pfe_handle* h, const T* prof, int64_t ps, int32_t lp, cons
                    (long long)ps, (long long)ds, lp, ld);
   if (n == 0) return PFE_OK;
   if (!prof || !dm || !out) return set_err(h, PFE_EINVAL, "lyon8: null buffer");
+  if (sizeof(T) == 4 && (((uintptr_t)prof | (uintptr_t)dm) & 3))
+    return set_err(h, PFE_EINVAL, "lyon8_f32: rows not 4-byte aligned");
   if (!is_u8 && (lp > (1 << 30) || ld > (1 << 30)))
     return set_err(h, PFE_EINVAL, "lyon8: row too long");
   if (is_u8 && (lp >= (1 << 24) || ld >= (1 << 24)))
@@ -539,6 +545,12 @@ int pfe_lyon8_f64(pfe_handle* h, const double* prof, int64_t ps, int32_t lp, con
                   int64_t ds, int32_t ld, int64_t n, double* out, uint32_t* status,
                   uint32_t flags) {
   return lyon8_impl<double>(h, prof, ps, lp, dm, ds, ld, n, out, status, flags, false);
+}
+
+int pfe_lyon8_f32(pfe_handle* h, const float* prof, int64_t ps, int32_t lp, const float* dm,
+                  int64_t ds, int32_t ld, int64_t n, double* out, uint32_t* status,
+                  uint32_t flags) {
+  return lyon8_impl<float>(h, prof, ps, lp, dm, ds, ld, n, out, status, flags, false);
 }
 
 }  // extern "C"
@@ -642,16 +654,20 @@ __global__ void k_params4(const double* scal, int64_t n, double* out, uint32_t* 
 
 // groups: pfe::BG_SINE (cols 0-3) / BG_GAUSS (4-10) / BG_DM (15-18, raw shift).  f64: the
 // profile rows are in->n x in->lp doubles at fprof (the float profile of a PFD), in->prof and
-// in->scal are not read
+// in->scal are not read.  prof32 (with f64, fprof null): the rows as floats, which
+// launch_widen_f32 widens into the layout's fprof for the same kernels
 static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* status,
                             uint32_t flags, const char* fn, unsigned groups, int c0, int k,
-                            bool f64 = false, const double* fprof = nullptr) {
+                            bool f64 = false, const double* fprof = nullptr,
+                            const float* prof32 = nullptr, bool f32 = false) {
   int64_t n;
   int rc = call_check(h, fn, in, out && status, n);
   if (rc || n == 0) return rc;
   const bool dm = groups == pfe::BG_DM;
-  if (f64 ? !fprof : (!in->scal || (dm ? !in->dmcurve : !in->prof)))
+  if (f64 ? (f32 ? !prof32 : !fprof) : (!in->scal || (dm ? !in->dmcurve : !in->prof)))
     return set_err(h, PFE_EINVAL, "%s: null input array", fn);
+  if (f32 && ((uintptr_t)prof32 & 3))
+    return set_err(h, PFE_EINVAL, "%s: prof not 4-byte aligned", fn);
   if (!dm && (in->lp < 8 || in->lp > 1024))
     return set_err(h, PFE_EINVAL, "%s: lp=%d outside [8,1024]", fn, in->lp);
   if (dm && (in->ndm < 3 || in->ndm > 1024))
@@ -674,7 +690,7 @@ static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, 
   const int cus = pfe::device_cus();
   pfe::GroupStage s;
   rc = lay_out(h, s, [&](pfe::Arena& A) {
-    return pfe::group_layout(A, n, g.lp, g.ndm, groups, f64, k, host, cus, h->opt);
+    return pfe::group_layout(A, n, g.lp, g.ndm, groups, f64, k, host, cus, h->opt, f32);
   });
   if (rc) return rc;
   if (host) {
@@ -682,6 +698,9 @@ static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, 
     if (dm) {
       rc = stage_in(h, s.dmcurve, in->dmcurve, m * g.ndm);
       g.dmcurve = s.dmcurve;
+    } else if (f32) {
+      rc = stage_in(h, s.prof32, prof32, m * g.lp);
+      prof32 = s.prof32;
     } else if (f64) {
       rc = stage_in(h, s.fprof, fprof, m * g.lp);
       fprof = s.fprof;
@@ -697,8 +716,14 @@ static int bates_group_call(pfe_handle* h, const pfe_bates_in* in, double* out, 
   }
   double* dk = host ? s.out : out;
   uint32_t* dst = host ? s.status : status;
-  hipError_t e = pfe::launch_bates_groups(&g, s.d22, dst, s.bates, st, &h->fork, h->opt, groups, dm,
-                                          f64 ? fprof : nullptr);
+  hipError_t e = hipSuccess;
+  if (f32) {
+    e = pfe::launch_widen_f32(prof32, s.fprof, n * g.lp, nullptr, nullptr, 0, st);
+    fprof = s.fprof;
+  }
+  if (e == hipSuccess)
+    e = pfe::launch_bates_groups(&g, s.d22, dst, s.bates, st, &h->fork, h->opt, groups, dm,
+                                 f64 ? fprof : nullptr);
   if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
   hipLaunchKernelGGL(k_take_cols, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, st, s.d22,
                      22, c0, k, n, dk);
@@ -746,6 +771,28 @@ int pfe_gauss7_f64(pfe_handle* h, const double* prof, int32_t lp, int64_t n, dou
                               7);
 }
 
+// the same on float32 profiles: widened once into the scratch, then the kernels of the f64 call
+static int bates_group_call_f32(pfe_handle* h, const float* prof, int32_t lp, int64_t n,
+                                double* out, uint32_t* status, uint32_t flags, const char* fn,
+                                unsigned groups, int c0, int k) {
+  pfe_bates_in in{};
+  in.lp = lp;
+  in.n = n;
+  return bates_group_call(h, &in, out, status, flags, fn, groups, c0, k, true, nullptr, prof, true);
+}
+
+int pfe_sinusoid4_f32(pfe_handle* h, const float* prof, int32_t lp, int64_t n, double* out,
+                      uint32_t* status, uint32_t flags) {
+  return bates_group_call_f32(h, prof, lp, n, out, status, flags, "sinusoid4_f32", pfe::BG_SINE,
+                              0, 4);
+}
+
+int pfe_gauss7_f32(pfe_handle* h, const float* prof, int32_t lp, int64_t n, double* out,
+                   uint32_t* status, uint32_t flags) {
+  return bates_group_call_f32(h, prof, lp, n, out, status, flags, "gauss7_f32", pfe::BG_GAUSS, 4,
+                              7);
+}
+
 int pfe_params4(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* status,
                 uint32_t flags) {
   int64_t n;
@@ -772,17 +819,25 @@ int pfe_params4(pfe_handle* h, const pfe_bates_in* in, double* out, uint32_t* st
 // ---- float sub-bands and the float 22-score call ------------------------------------------
 // pfe_subband3_f64 (chain = false: out n x 3) and pfe_bates22_f64 (chain: the 22 scores): on
 // the host path the inputs go to the scratch and the results come back; the launchers of
-// subband_f64.hip work behind them
-static int score_f64_call(pfe_handle* h, const pfe_bates_f64_in* in, double* out, uint32_t* status,
-                          uint32_t flags, const char* fn, bool chain) {
+// subband_f64.hip work behind them.  In = pfe_bates_f32_in: the _f32 calls, with the float
+// arrays held (and staged) as floats and the launchers of cand_f32.hip
+template <class In>
+static int score_float_call(pfe_handle* h, const In* in, double* out, uint32_t* status,
+                            uint32_t flags, const char* fn, bool chain) {
+  constexpr bool F32 = std::is_same<In, pfe_bates_f32_in>::value;
+  constexpr uintptr_t amask = F32 ? 3 : 7;  // of the float arrays
   int64_t n;
   int rc = call_check(h, fn, in, out && status, n);
   if (rc || n == 0) return rc;
   if (!in->prof || !in->sub || !in->scal || (chain && !in->dmcurve))
     return set_err(h, PFE_EINVAL, "%s: null input array", fn);
-  if ((((uintptr_t)in->prof | (uintptr_t)in->sub | (uintptr_t)in->scal | (uintptr_t)out) & 7) ||
-      (chain && ((uintptr_t)in->dmcurve & 7)))
-    return set_err(h, PFE_EINVAL, "%s: array not 8-byte aligned", fn);
+  if ((((uintptr_t)in->scal | (uintptr_t)out) & 7) ||
+      (((uintptr_t)in->prof | (uintptr_t)in->sub) & amask) ||
+      (chain && ((uintptr_t)in->dmcurve & amask)))
+    return set_err(h, PFE_EINVAL,
+                   F32 ? "%s: array not aligned (4 bytes: prof, sub, dmcurve; 8: scal, out)"
+                       : "%s: array not 8-byte aligned",
+                   fn);
   if (chain ? (in->lp < 8 || in->lp > 1024) : in->lp < 1)
     return set_err(h, PFE_EINVAL, "%s: lp=%d outside [%d,%d]", fn, in->lp, chain ? 8 : 1,
                    chain ? 1024 : INT32_MAX);
@@ -800,12 +855,15 @@ static int score_f64_call(pfe_handle* h, const pfe_bates_f64_in* in, double* out
   const int cus = pfe::device_cus();
   const pfe::SubF64Plan p = pfe::subf64_plan(in->nsub, in->lsb, n, cus, h->opt.subf64_global != 0);
   const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
-  pfe::SubF64Stage s;
+  typename std::conditional<F32, pfe::SubF32Stage, pfe::SubF64Stage>::type s;
   rc = lay_out(h, s, [&](pfe::Arena& A) {
-    return pfe::subband_f64_layout(A, *in, host, chain, p.slab_bytes(), cus, h->opt);
+    if constexpr (F32)
+      return pfe::subband_f32_layout(A, *in, host, chain, p.slab_bytes(), cus, h->opt);
+    else
+      return pfe::subband_f64_layout(A, *in, host, chain, p.slab_bytes(), cus, h->opt);
   });
   if (rc) return rc;
-  pfe_bates_f64_in din = *in;
+  In din = *in;
   if (host) {
     const size_t m = (size_t)n;
     if ((rc = stage_in(h, s.prof, in->prof, m * in->lp)) ||
@@ -821,9 +879,15 @@ static int score_f64_call(pfe_handle* h, const pfe_bates_f64_in* in, double* out
   double* dout = host ? s.out : out;
   uint32_t* dstat = host ? s.status : status;
   hipStream_t st = h->stream;
-  hipError_t e = chain ? pfe::launch_bates22_f64(&din, dout, dstat, s.bates, p, s.slabs, st,
-                                                 &h->fork, h->opt)
-                       : pfe::launch_subband_f64(&din, dout, 3, dstat, false, p, s.slabs, st);
+  hipError_t e;
+  if constexpr (F32)
+    e = chain ? pfe::launch_bates22_f32(&din, s.fprof, s.fdm, dout, dstat, s.bates, p, s.slabs, st,
+                                        &h->fork, h->opt)
+              : pfe::launch_subband_f32(&din, dout, 3, dstat, false, p, s.slabs, st);
+  else
+    e = chain ? pfe::launch_bates22_f64(&din, dout, dstat, s.bates, p, s.slabs, st, &h->fork,
+                                        h->opt)
+              : pfe::launch_subband_f64(&din, dout, 3, dstat, false, p, s.slabs, st);
   if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
   if (host && (rc = fetch_out(h, out, dout, chain ? 22 : 3, status, dstat, n))) return rc;
   return call_end(h);
@@ -833,12 +897,22 @@ extern "C" {
 
 int pfe_subband3_f64(pfe_handle* h, const pfe_bates_f64_in* in, double* out, uint32_t* status,
                      uint32_t flags) {
-  return score_f64_call(h, in, out, status, flags, "subband3_f64", false);
+  return score_float_call(h, in, out, status, flags, "subband3_f64", false);
 }
 
 int pfe_bates22_f64(pfe_handle* h, const pfe_bates_f64_in* in, double* out, uint32_t* status,
                     uint32_t flags) {
-  return score_f64_call(h, in, out, status, flags, "bates22_f64", true);
+  return score_float_call(h, in, out, status, flags, "bates22_f64", true);
+}
+
+int pfe_subband3_f32(pfe_handle* h, const pfe_bates_f32_in* in, double* out, uint32_t* status,
+                     uint32_t flags) {
+  return score_float_call(h, in, out, status, flags, "subband3_f32", false);
+}
+
+int pfe_bates22_f32(pfe_handle* h, const pfe_bates_f32_in* in, double* out, uint32_t* status,
+                    uint32_t flags) {
+  return score_float_call(h, in, out, status, flags, "bates22_f32", true);
 }
 
 // ---- PFD -------------------------------------------------------------------------------

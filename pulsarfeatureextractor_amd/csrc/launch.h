@@ -17,6 +17,9 @@ hipError_t launch_lyon8_u8(const uint8_t* prof, int64_t ps, int lp, const uint8_
 hipError_t launch_lyon8_f64(const double* prof, int64_t ps, int lp, const double* dm,
                             int64_t ds, int ld, int64_t n, double* out, hipStream_t st,
                             const Options& o);
+// float32 rows (pfe_lyon8_f32): the kernels of launch_lyon8_f64 loading floats, widened at the load
+hipError_t launch_lyon8_f32(const float* prof, int64_t ps, int lp, const float* dm, int64_t ds,
+                            int ld, int64_t n, double* out, hipStream_t st, const Options& o);
 hipError_t launch_sine(const BatesArgs& a, hipStream_t st);
 hipError_t launch_gauss(const BatesArgs& a, hipStream_t st);
 hipError_t launch_dmfit(const BatesArgs& a, hipStream_t st);
@@ -247,29 +250,82 @@ inline SubF64Stage subband_f64_layout(Arena& A, const pfe_bates_f64_in& in, bool
   return s;
 }
 
+// ---- float32 candidates: the _f32 forms of the float-array calls (cand_f32.hip) -----------
+// da[i] = (double)a[i], i < na, and db[i] = (double)b[i], i < nb (nb = 0: a alone): the small
+// per-candidate arrays the fit kernels read many times (profiles, DM curves), widened once
+hipError_t launch_widen_f32(const float* a, double* da, int64_t na, const float* b, double* db,
+                            int64_t nb, hipStream_t st);
+// launch_subband_f64 on float32 arrays: the copy of a candidate's sub-bands and its profile row
+// are widened on their way into the LDS or the slab; plan, slabs and arithmetic are the f64 call's
+hipError_t launch_subband_f32(const pfe_bates_f32_in* in, double* out, int ldo, uint32_t* status,
+                              bool chain, const SubF64Plan& p, void* slabs, hipStream_t st);
+// pfe_bates22_f32: launch_widen_f32 of the profiles into fprof (n x lp) and the DM curves into
+// fdm (n x ndm) on st, then the schedule of launch_bates22_f64 with launch_subband_f32
+hipError_t launch_bates22_f32(const pfe_bates_f32_in* in, double* fprof, double* fdm, double* out,
+                              uint32_t* status, const BatesArgs& work, const SubF64Plan& p,
+                              void* slabs, hipStream_t st, const Fork* fk, const Options& o);
+
+// pfe_subband3_f32 / pfe_bates22_f32: subband_f64_layout with the staged float arrays as the
+// floats they are, and (chain, host pointers or device) the widened profiles and DM curves
+// behind them.  The sub-bands are never widened in memory.
+struct SubF32Stage {
+  float *prof = nullptr, *sub = nullptr, *dmcurve = nullptr;
+  double *scal = nullptr, *out = nullptr;
+  uint32_t* status = nullptr;
+  double *fprof = nullptr, *fdm = nullptr;  // pfe_bates22_f32
+  BatesArgs bates;                          // pfe_bates22_f32
+  void* slabs = nullptr;
+};
+inline SubF32Stage subband_f32_layout(Arena& A, const pfe_bates_f32_in& in, bool host, bool chain,
+                                      size_t slab_bytes, int cus, const Options& o) {
+  SubF32Stage s{};
+  const size_t n = (size_t)in.n;
+  if (host) {
+    s.prof = A.take<float>(n * in.lp, "prof");
+    s.sub = A.take<float>(n * in.nsub * in.lsb, "sub");
+    if (chain) s.dmcurve = A.take<float>(n * in.ndm, "dmcurve");
+    s.scal = A.take<double>(n * PFE_NSCAL, "scal");
+    s.out = A.take<double>(n * (chain ? 22 : 3), "out");
+    s.status = A.take<uint32_t>(n, "status");
+  }
+  if (chain) {
+    s.fprof = A.take<double>(n * in.lp, "fprof");
+    s.fdm = A.take<double>(n * in.ndm, "fdm");
+    bates_layout(A, s.bates, in.n, in.lp, 0, cus, o);
+  }
+  if (slab_bytes) s.slabs = A.take<char>(slab_bytes, "slabs");
+  return s;
+}
+
 // one score group of n candidates (groups: BG_SINE / BG_GAUSS / BG_DM; 0: pfe_params4, which
 // fits nothing).  A fit scores into a 22-column scratch d22 and hands out its k columns.
 // Inputs: the DM curves (BG_DM: lp = 0), the float profiles (f64) or the byte profiles, and
-// the scalars of every call but the f64 ones.
+// the scalars of every call but the f64 ones.  The float32 forms (f32, with f64): the profiles
+// staged as the floats they are (prof32), and fprof -- host pointers or device -- for
+// launch_widen_f32 to fill; the fit kernels read fprof as in the f64 call.
 struct GroupStage {
   uint8_t* prof = nullptr;
+  float* prof32 = nullptr;
   double *fprof = nullptr, *dmcurve = nullptr, *scal = nullptr, *d22 = nullptr, *out = nullptr;
   uint32_t* status = nullptr;
   BatesArgs bates;
 };
 inline GroupStage group_layout(Arena& A, int64_t n_, int lp, int ndm, unsigned groups, bool f64,
-                               int k, bool host, int cus, const Options& o) {
+                               int k, bool host, int cus, const Options& o, bool f32 = false) {
   GroupStage s{};
   const size_t n = (size_t)n_;
   if (host) {
     if (groups == BG_DM)
       s.dmcurve = A.take<double>(n * ndm, "dmcurve");
+    else if (f32)
+      s.prof32 = A.take<float>(n * lp, "prof32");
     else if (f64)
       s.fprof = A.take<double>(n * lp, "fprof");
     else if (groups)
       s.prof = A.take<uint8_t>(n * lp, "prof");
     if (!f64) s.scal = A.take<double>(n * PFE_NSCAL, "scal");
   }
+  if (f32) s.fprof = A.take<double>(n * lp, "fprof");
   if (groups) s.d22 = A.take<double>(n * 22, "d22");
   if (host) {
     s.out = A.take<double>(n * k, "out");

@@ -1397,10 +1397,11 @@ void lyon8_u8_dm(const uint8_t* __restrict__ prof, int64_t ps, const uint8_t* __
 // x - mean).  NC: both lengths <= np_inl_max(3) = 968, every level of the pairwise tree
 // inlined; else one call per level (254 VGPRs and a stack, one wave per SIMD: a first
 // correct version for rows that long).
-template <bool NC>
-__global__ __launch_bounds__(256) void lyon8_f64_generic(const double* __restrict__ prof,
+// T: the rows' element type, double or float (pfe_lyon8_f32: widened at the load, np_sum.h).
+template <bool NC, typename T>
+__global__ __launch_bounds__(256) void lyon8_f64_generic(const T* __restrict__ prof,
                                                          int64_t ps, int lp,
-                                                         const double* __restrict__ dm,
+                                                         const T* __restrict__ dm,
                                                          int64_t ds, int ld, int64_t n,
                                                          double* __restrict__ out) {
   const int lane = threadIdx.x & 63;
@@ -1414,7 +1415,7 @@ __global__ __launch_bounds__(256) void lyon8_f64_generic(const double* __restric
     const int64_t c = (u >> 1) * 8 + g;
     const bool own = c < n;
     const int64_t cr = own ? c : n - 1;  // idle groups redo the last row: every lane stays active
-    const double* p = row ? dm + cr * ds : prof + cr * ps;
+    const T* p = row ? dm + cr * ds : prof + cr * ps;
     const int len = row ? ld : lp;
     double o[4];
     stats4_f64_g8<NC>(p, len, t, o);
@@ -1705,16 +1706,28 @@ hipError_t launch_lyon8_u8(const uint8_t* prof, int64_t ps, int lp, const uint8_
   return hipGetLastError();
 }
 
-hipError_t launch_lyon8_f64(const double* prof, int64_t ps, int lp, const double* dm,
-                            int64_t ds, int ld, int64_t n, double* out, hipStream_t st,
-                            const Options& o) {
+template <typename T>
+static hipError_t launch_lyon8_rows(const T* prof, int64_t ps, int lp, const T* dm, int64_t ds,
+                                    int ld, int64_t n, double* out, hipStream_t st,
+                                    const Options& o) {
   if (n <= 0) return hipSuccess;
   const int grid = grid_for(2 * ((n + 7) / 8), o.lyon8_blocks);  // a wave per 8 rows
   if (lp <= np_inl_max(3) && ld <= np_inl_max(3))
-    hipLaunchKernelGGL(lyon8_f64_generic<true>, dim3(grid), dim3(256), 0, st, prof, ps, lp, dm, ds, ld, n, out);
+    hipLaunchKernelGGL((lyon8_f64_generic<true, T>), dim3(grid), dim3(256), 0, st, prof, ps, lp, dm, ds, ld, n, out);
   else
-    hipLaunchKernelGGL(lyon8_f64_generic<false>, dim3(grid), dim3(256), 0, st, prof, ps, lp, dm, ds, ld, n, out);
+    hipLaunchKernelGGL((lyon8_f64_generic<false, T>), dim3(grid), dim3(256), 0, st, prof, ps, lp, dm, ds, ld, n, out);
   return hipGetLastError();
+}
+
+hipError_t launch_lyon8_f64(const double* prof, int64_t ps, int lp, const double* dm,
+                            int64_t ds, int ld, int64_t n, double* out, hipStream_t st,
+                            const Options& o) {
+  return launch_lyon8_rows(prof, ps, lp, dm, ds, ld, n, out, st, o);
+}
+
+hipError_t launch_lyon8_f32(const float* prof, int64_t ps, int lp, const float* dm, int64_t ds,
+                            int ld, int64_t n, double* out, hipStream_t st, const Options& o) {
+  return launch_lyon8_rows(prof, ps, lp, dm, ds, ld, n, out, st, o);
 }
 
 }  // namespace pfe

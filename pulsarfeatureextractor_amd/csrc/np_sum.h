@@ -197,14 +197,15 @@ __device__ __forceinline__ SumK<K> np_sum_g8(Fn f, int n, int t) {
 // numpy.mean / numpy.std / scipy.stats.skew / scipy.stats.kurtosis of eight float64 rows of
 // n values per wave (row lane / 8 at x, in LDS or global memory): the deviations are formed
 // from the row and the mean in the pass that sums their powers (d^3 = d^2 d, d^4 = (d^2)^2,
-// scipy's _moment), so no scratch row.
-template <bool NC>
-__device__ __forceinline__ void stats4_f64_g8(const double* x, int n, int t, double (&o)[4]) {
-  auto fx = [x](int i, double (&v)[1]) { v[0] = x[i]; };
+// scipy's _moment), so no scratch row.  T = float: the row is held as float32 and each value
+// widened (exactly) at its load, in both passes; every operation is fp64 as for T = double.
+template <bool NC, typename T>
+__device__ __forceinline__ void stats4_f64_g8(const T* x, int n, int t, double (&o)[4]) {
+  auto fx = [x](int i, double (&v)[1]) { v[0] = (double)x[i]; };
   const SumK<1> s = np_sum_g8<NC, 1>(fx, n, t);
   const double mean = s.v[0] / (double)n;
   auto fd = [x, mean](int i, double (&v)[3]) {
-    const double d = x[i] - mean;
+    const double d = (double)x[i] - mean;
     const double d2 = d * d;
     v[0] = d2;
     v[1] = d2 * d;

@@ -272,12 +272,20 @@ class PHCXOperations(ProfileOperations):
 
     def getSubbandParameters_batch(self, profiles, subbands, scal):
         """Byte-valued profiles and sub-bands (the rule of _profile_rows) go to pfe_subband3;
-        anything else (normalised or baseline-subtracted data) to pfe_subband3_f64."""
+        anything else (normalised or baseline-subtracted data) to pfe_subband3_f64 -- or, when
+        the profile and the sub-bands are both float32, to pfe_subband3_f32 as they are, with
+        nothing widened on the host (the same values: pfe.h)."""
         scal = np.asarray(scal, dtype=np.float64)
-        prof, pf = _profile_rows(profiles)
         sub = np.asarray(subbands)
         sf = sub.dtype != np.uint8 and bool(sub.size) and (
             sub.min() < 0 or sub.max() > 255 or not np.array_equal(sub, np.round(sub)))
+        if isinstance(profiles, np.ndarray) and profiles.dtype == np.float32 and sub.dtype == np.float32:
+            p32 = profiles[None, :] if profiles.ndim == 1 else profiles
+            if sf or (p32.size and (p32.min() < 0 or p32.max() > 255 or
+                                    not np.array_equal(p32, np.round(p32)))):
+                return self.engine.subband3_f32(np.ascontiguousarray(p32), np.ascontiguousarray(sub),
+                                                scal)
+        prof, pf = _profile_rows(profiles)
         if pf or sf:
             return self.engine.subband3_f64(np.ascontiguousarray(prof, dtype=np.float64),
                                             np.ascontiguousarray(sub, dtype=np.float64), scal)

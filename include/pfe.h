@@ -54,6 +54,7 @@ extern "C" {
 
 /* flags */
 #define PFE_FLAG_DEVICE_PTRS 0x1u /* all array arguments are device pointers */
+/* PFE_FLAG_PFD_AVGPROF 0x2u: the PFD calls only; defined with pfe_pfd_avgprof below */
 
 /* Per-candidate status bits (pfe_bates22).  A non-zero status means the reference would
  * have raised inside Candidate.calculateScores and DataProcessor would have logged the
@@ -433,7 +434,8 @@ int pfe_pfd_subband3(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t*
  * and the f64 kernels run on S as folds of one part.  This is NOT numpy.sum of a float32
  * array, which accumulates in float32: compare with profs.astype(numpy.float64) scored by the
  * f64 call, or summed in fp64.  The header scalars (PFE_PFD_AVGPROF, PFE_PFD_VARPROF and the
- * others) stay fp64 and stay the caller's to supply.
+ * others) stay fp64 and stay the caller's to supply -- but for PFE_PFD_AVGPROF, which
+ * PFE_FLAG_PFD_AVGPROF (below) derives from the floats on the device.
  *
  * Shape limits, PFE_EINVAL texts, status bits, stream behaviour, PFE_FLAG_DEVICE_PTRS and
  * the routing options (PFE_OPT_PFD_WAVES, _SPLIT, _GLOBAL) are those of the f64 call of the
@@ -462,6 +464,52 @@ int pfe_pfd_dmfit4_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uin
                        uint32_t flags);
 int pfe_pfd_subband3_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uint32_t* status,
                          uint32_t flags);
+
+/* ---- a fold's average, derived where the cube is ---------------------------------------
+ * scal[PFE_PFD_AVGPROF] is the one per-fold input that is a function of the cube alone:
+ * PFDFile.load's self.avgprof = (self.profs / self.proflen).sum() (PFDFile.py:225), which the
+ * chi^2-vs-DM sweep subtracts from every bin (calc_redchi2, :427-438).  A fold that is already
+ * on the device -- or a cube the caller does not want to pass over twice on the host -- gets
+ * it here, with numpy's bits.
+ *
+ * Contract: out[i * out_stride] is, bit for bit, numpy's (x / proflen).sum() of fold i's
+ * E = npart x nsub x proflen values x in memory order (float64; a float32 cube widened value
+ * by value first, profs.astype(numpy.float64): nothing is divided or added in float32):
+ *   y[e] = (double)x[e] / (double)proflen, the correctly rounded fp64 quotient (a power-of-two
+ *          proflen scales by its exact reciprocal: the same bits);
+ *   c[k] = numpy's pairwise sum of y[8192 k .. 8192 k + 8191] (the last chunk shorter): n < 8
+ *          values 0.0 + y0 + y1 ..., n <= 128 in eight accumulators r[t] = y[t] + y[t + 8] +
+ *          ... combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the n % 8 last in order,
+ *          more than 128 split at floor8(n / 2);
+ *   out  = 0.0 + c[0] + c[1] + c[2] + ..., in order onto numpy's initial 0.0 (which shows in
+ *          one case: a fold whose values are all -0.0 gives +0.0, whatever its size).
+ * This is NOT one pairwise tree over the cube, and not torch.sum.  inf, NaN, subnormal
+ * quotients and overflow come out as numpy's.
+ *
+ * Any npart >= 1, nsub >= 1 and proflen >= 2: the call only streams the cube, so it has no LDS
+ * shape limit.  out_stride >= 1, in doubles: with out = &scal[PFE_PFD_AVGPROF] and out_stride =
+ * PFE_PFD_NSCAL the values land in the scal array of a PFD call and nothing else of it is
+ * written.  PFE_EINVAL for a null array, a negative size, out_stride < 1 or a float cube that
+ * is not 4-byte aligned.  Stream behaviour and PFE_FLAG_DEVICE_PTRS as the PFD calls; a
+ * host-pointer call stages the cube in the handle's scratch.  Scratch: n x ceil(E / 8192)
+ * doubles of chunk sums behind what a host-pointer call stages.
+ *
+ * PFE_FLAG_PFD_AVGPROF, on any of the ten PFD calls (f64 and _f32): scal[i][PFE_PFD_AVGPROF]
+ * is not read; the call uses what pfe_pfd_avgprof gives for the cube as the call holds it on
+ * the device -- a host-pointer call derives it from the copy it staged (the cube crosses the
+ * bus once), a float32 call pass by pass (PFE_OPT_PFD_F32_CHUNK) from the floats -- written
+ * into a scratch copy of scal that the kernels then read.  The caller's scal is never written
+ * (a device-pointer call takes n x PFE_PFD_NSCAL doubles of scratch for the copy).  Every
+ * output is the bits of the unflagged call given that value.  pfe_pfd_params4, pfe_pfd_subband3
+ * and their _f32 forms do not read the average: they accept the flag and do no extra work.
+ * Without the flag every call does what it did before. */
+#define PFE_FLAG_PFD_AVGPROF 0x2u /* PFD calls: derive scal[PFE_PFD_AVGPROF] from the cube */
+
+int pfe_pfd_avgprof(pfe_handle* h, const double* profs, int32_t npart, int32_t nsub,
+                    int32_t proflen, int64_t n, double* out, int64_t out_stride, uint32_t flags);
+int pfe_pfd_avgprof_f32(pfe_handle* h, const float* profs, int32_t npart, int32_t nsub,
+                        int32_t proflen, int64_t n, double* out, int64_t out_stride,
+                        uint32_t flags);
 
 /* ---- float32 candidates: the float-array calls on arrays of floats ----------------------
  * A candidate that never was a .pfd or .phcx file -- a float32 tensor from a GPU folder or a

@@ -66,7 +66,11 @@ EXPORTED_SYMBOLS = (
     "pfe_gauss7_f32",
     "pfe_subband3_f32",
     "pfe_bates22_f32",
+    "pfe_pfd_avgprof",
+    "pfe_pfd_avgprof_f32",
 )
+PFE_FLAG_PFD_AVGPROF = 0x2  # PFD calls: derive scal[:, PFE_PFD_AVGPROF] from the cube
+PFE_PFD_AVGPROF = 2
 PFE_PFD_NSCAL = 8
 PFE_PFD_NDM = 100
 PFE_ST_PFD_DMCURVE_FAIL = 0x020
@@ -219,6 +223,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         f64 = [vp, vp, i32, i64, vp, vp, u32]
         bates_f64 = [vp, ptr(BatesF64In), vp, vp, u32]
         bates_f32 = [vp, ptr(BatesF32In), vp, vp, u32]
+        avg = [vp, vp, i32, i32, i32, i64, vp, i64, u32]
         signatures = {  # name: (restype, argtypes), as include/pfe.h and include/pfe_io.h declare
             "pfe_abi_version": (rc, []), "pfe_device_count": (rc, []),
             "pfe_create": (rc, [C.c_int, ptr(vp)]), "pfe_destroy": (None, [vp]),
@@ -241,6 +246,7 @@ def load_library(path: str | None = None) -> C.CDLL:
             "pfe_lyon8_f32": (rc, lyon),
             "pfe_sinusoid4_f32": (rc, f64), "pfe_gauss7_f32": (rc, f64),
             "pfe_subband3_f32": (rc, bates_f32), "pfe_bates22_f32": (rc, bates_f32),
+            "pfe_pfd_avgprof": (rc, avg), "pfe_pfd_avgprof_f32": (rc, avg),
             "pfe_phcx_parse": (rc, [ptr(C.c_char_p), i64, i32, i32, ptr(vp)]),
             "pfe_phcx_count": (i64, [vp]),
             "pfe_phcx_info_get": (rc, [vp, i64, ptr(PhcxInfo)]),
@@ -758,12 +764,41 @@ class Engine:
         """The C entry point of a PFD call: its _f32 form for a float32 cube."""
         return getattr(self.lib, "pfe_" + fn + ("_f32" if isinstance(pin, PfdF32In) else ""))
 
-    def pfd_dmprof(self, profs, subfreqs, scal, profile=True, chis=True, lyon8=True):
+    def pfd_avgprof(self, profs):
+        """numpy's (profs / proflen).sum() of each fold of a (n,npart,nsub,L) cube, bit for
+        bit (pfe_pfd_avgprof; a float32 cube -- numpy array or device tensor -- goes to
+        pfe_pfd_avgprof_f32 as it is and gives the value of profs.astype(float64)): the
+        scal[:, 2] every PFD call reads.  Returns (n,) float64 where the cube lives."""
+        if profs.ndim != 4:
+            raise ValueError("pfd_avgprof: profs must be (n,npart,nsub,L)")
+        n, npart, nsub, L = profs.shape
+        if _is_device(profs):
+            import torch
+
+            self._dev(profs, "profs", (torch.float64, torch.float32))
+            self._follow_torch()
+            f32 = profs.dtype == torch.float32
+            out = torch.empty((n,), dtype=torch.float64, device=profs.device)
+            flags = PFE_FLAG_DEVICE_PTRS
+        else:
+            f32 = isinstance(profs, np.ndarray) and profs.dtype == np.float32
+            profs = np.ascontiguousarray(profs, dtype=np.float32 if f32 else np.float64)
+            out = np.empty((n,), dtype=np.float64)
+            flags = 0
+        fn = self.lib.pfe_pfd_avgprof_f32 if f32 else self.lib.pfe_pfd_avgprof
+        self._check(fn(self._h, _ptr(profs), npart, nsub, L, n, _ptr(out), 1, flags))
+        return out
+
+    def pfd_dmprof(self, profs, subfreqs, scal, profile=True, chis=True, lyon8=True,
+                   derive_avgprof=False):
         """PFD preprocessing + Lyon features (pfe_pfd_dmprof) for a batch of folds of one
         shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL).
         A float32 cube (numpy array or device tensor) is scored as it is, by the _f32 call of
         this and the other PFD methods: the bits of the f64 call on profs widened to f64
         (parts summed in fp64; not numpy's float32 sum).  subfreqs and scal stay f64.
+        derive_avgprof (this and the other PFD methods): scal[:, 2] is not read; the library
+        derives it from the cube on the device (PFE_FLAG_PFD_AVGPROF, the value of
+        pfd_avgprof), and scal is left as it is.
         Returns dict(profile (n,L) f64, chis (n,100) f32, lyon8 (n,8) f64, status (n,))."""
         pin, dev, keep = self._pfd_args(profs, subfreqs, scal, "pfd_dmprof")
         n, L = pin.n, pin.proflen
@@ -778,6 +813,8 @@ class Engine:
             mk = lambda shape, dt: np.empty(shape, dtype=dt)  # noqa: E731
             f64, f32, i32 = np.float64, np.float32, np.uint32
             flags = 0
+        if derive_avgprof:
+            flags |= PFE_FLAG_PFD_AVGPROF
         out["profile"] = mk((n, L), f64) if profile else None
         out["chis"] = mk((n, PFE_PFD_NDM), f32) if chis else None
         out["lyon8"] = mk((n, 8), f64) if lyon8 else None
@@ -789,31 +826,37 @@ class Engine:
         del keep
         return out
 
-    def _pfd_scores(self, fn, k, profs, subfreqs, scal, out, status):
+    def _pfd_scores(self, fn, k, profs, subfreqs, scal, out, status, derive_avgprof=False):
         pin, dev, keep = self._pfd_args(profs, subfreqs, scal, fn)
         out, status, flags = self._outputs(dev, profs, pin.n, k, out, status)
+        if derive_avgprof:
+            flags |= PFE_FLAG_PFD_AVGPROF
         self._check(self._pfd_fn(fn, pin)(self._h, C.byref(pin), _ptr(out), _ptr(status), flags))
         del keep
         return out, status
 
-    def pfd_bates22(self, profs, subfreqs, scal, out=None, status=None):
+    def pfd_bates22(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False):
         """The 22 scores of PFD folds (pfe_pfd_bates22, PFDFile.compute) for a batch of one
         shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL) with
         scal[:, 7] = bary_p1.  Returns (out (n,22) f64, status (n,))."""
-        return self._pfd_scores("pfd_bates22", 22, profs, subfreqs, scal, out, status)
+        return self._pfd_scores("pfd_bates22", 22, profs, subfreqs, scal, out, status,
+                                derive_avgprof)
 
     # one score group of a batch of folds (PFDOperations; inputs as pfd_bates22)
-    def pfd_params4(self, profs, subfreqs, scal, out=None, status=None):
+    def pfd_params4(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False):
         """getCandidateParameters (pfe_pfd_params4): [period_ms, snr, dm, width], unfiltered."""
-        return self._pfd_scores("pfd_params4", 4, profs, subfreqs, scal, out, status)
+        return self._pfd_scores("pfd_params4", 4, profs, subfreqs, scal, out, status,
+                                derive_avgprof)
 
-    def pfd_dmfit4(self, profs, subfreqs, scal, out=None, status=None):
+    def pfd_dmfit4(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False):
         """getDMFittings (pfe_pfd_dmfit4): [s16, s17, Shift (signed), s19]."""
-        return self._pfd_scores("pfd_dmfit4", 4, profs, subfreqs, scal, out, status)
+        return self._pfd_scores("pfd_dmfit4", 4, profs, subfreqs, scal, out, status,
+                                derive_avgprof)
 
-    def pfd_subband3(self, profs, subfreqs, scal, out=None, status=None):
+    def pfd_subband3(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False):
         """getSubbandParameters (pfe_pfd_subband3): s20-s22."""
-        return self._pfd_scores("pfd_subband3", 3, profs, subfreqs, scal, out, status)
+        return self._pfd_scores("pfd_subband3", 3, profs, subfreqs, scal, out, status,
+                                derive_avgprof)
 
 
 class PhcxBatch:

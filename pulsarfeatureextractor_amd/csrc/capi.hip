@@ -14,6 +14,7 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "../../include/pfe.h"
 #include "launch.h"
@@ -1005,6 +1006,33 @@ static int pfd_pass(pfe_handle* h, const char* fn, const pfe::PfdArgs& a, const 
   return PFE_OK;
 }
 
+// PFE_FLAG_PFD_AVGPROF: where the derived averages go -- the scal a host-pointer call staged
+// (`staged`), or, device pointers (null), a copy of the caller's scal in scratch -- and `a`
+// reads its scalars there
+static int pfd_avg_begin(pfe_handle* h, const pfe_pfd_in* in, double* staged,
+                         const pfe::PfdAvgWork& w, pfe::PfdArgs& a, double*& wscal) {
+  wscal = staged;
+  if (!staged) {
+    PFE_HIP(h, hipMemcpyAsync(w.scal, in->scal, (size_t)in->n * PFE_PFD_NSCAL * sizeof(double),
+                              hipMemcpyDeviceToDevice, h->stream));
+    wscal = w.scal;
+  }
+  a.scal = wscal;
+  return PFE_OK;
+}
+// the averages of folds [c0, c0 + cn) of the batch `a` into their rows of wscal, from the cube
+// as the call holds it on the device (x32: the floats of an _f32 call)
+static int pfd_avg_pass(pfe_handle* h, const char* fn, const pfe::PfdArgs& a, const float* x32,
+                        int64_t c0, int64_t cn, double* csum, double* wscal) {
+  const int64_t E = (int64_t)a.npart * a.nsub * a.L;
+  double* out = wscal + c0 * PFE_PFD_NSCAL + PFE_PFD_AVGPROF;
+  const hipError_t e =
+      x32 ? pfe::launch_pfd_avgprof_f32(x32 + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL, h->stream)
+          : pfe::launch_pfd_avgprof(a.profs + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL, h->stream);
+  if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
+  return PFE_OK;
+}
+
 // pfe_pfd_dmprof, and pfe_pfd_dmprof_f32 (f32: the cube is x32, in->profs is not read)
 static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const float* x32,
                            double* profile, float* chis, double* lyon8, uint32_t* status,
@@ -1037,11 +1065,15 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
       if (!v) PFE_HIP(h, hipEventCreateWithFlags(&v, hipEventDisableTiming));
   }
   const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
+  const bool derive = flags & PFE_FLAG_PFD_AVGPROF;
   pfe::PfdDmprofStage s;
   rc = lay_out(h, s, [&](pfe::Arena& A) {
-    return pfe::pfd_dmprof_layout(A, *in, host, profile, chis, lyon8, ws_bytes, f32 ? pass : 0);
+    return pfe::pfd_dmprof_layout(A, *in, host, profile, chis, lyon8, ws_bytes, f32 ? pass : 0,
+                                  derive);
   });
   if (rc || (host && (rc = stage_pfd(h, in, x32, s.in, a)))) return rc;
+  double* wscal = nullptr;
+  if (derive && (rc = pfd_avg_begin(h, in, host ? s.in.scal : nullptr, s.avg, a, wscal))) return rc;
   a.profile = host ? s.profile : profile;
   a.chis = host ? s.chis : chis;
   a.lyon8 = host ? s.lyon8 : lyon8;
@@ -1049,6 +1081,7 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   for (int64_t c0 = 0; c0 < n; c0 += pass) {
     const int64_t cn = n - c0 < pass ? n - c0 : pass;
     pfe::PfdArgs b;
+    if (derive && (rc = pfd_avg_pass(h, "pfd_dmprof", a, x32, c0, cn, s.avg.csum, wscal))) return rc;
     if ((rc = pfd_pass(h, "pfd_dmprof", a, x32, s.in.psum, c0, cn, b))) return rc;
     if (a.profile) b.profile = a.profile + c0 * a.L;
     if (a.chis) b.chis = a.chis + c0 * PFE_PFD_NDM;
@@ -1072,6 +1105,67 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
       return rc;
   }
   return call_end(h);
+}
+
+// pfe_pfd_avgprof (xd) / pfe_pfd_avgprof_f32 (xf): the other cube is null
+static int pfd_avgprof_call(pfe_handle* h, const double* xd, const float* xf, bool f32, int npart,
+                            int nsub, int proflen, int64_t n, double* out, int64_t out_stride,
+                            uint32_t flags) {
+  if (!h) return PFE_EINVAL;
+  h->err.clear();
+  if ((f32 ? !xf : !xd) || !out) return set_err(h, PFE_EINVAL, "pfd_avgprof: null argument");
+  if (n < 0) return set_err(h, PFE_EINVAL, "pfd_avgprof: n < 0");
+  if (npart < 1 || nsub < 1 || proflen < 2)
+    return set_err(h, PFE_EINVAL, "pfd_avgprof: shape %dx%dx%d", npart, nsub, proflen);
+  if (out_stride < 1) return set_err(h, PFE_EINVAL, "pfd_avgprof: out_stride < 1");
+  if (f32 && ((uintptr_t)xf & 3))
+    return set_err(h, PFE_EINVAL, "pfd_avgprof: profs not 4-byte aligned");
+  if (n == 0) return PFE_OK;
+  int rc = call_begin(h);
+  if (rc) return rc;
+  const int64_t E = (int64_t)npart * nsub * proflen;
+  const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
+  pfe::PfdAvgStage s;
+  rc = lay_out(h, s, [&](pfe::Arena& A) { return pfe::pfd_avgprof_layout(A, E, n, host, f32); });
+  if (rc) return rc;
+  if (host) {
+    if ((rc = f32 ? stage_in(h, s.profs32, xf, (size_t)n * E) : stage_in(h, s.profs, xd, (size_t)n * E)))
+      return rc;
+    xf = s.profs32;
+    xd = s.profs;
+  }
+  double* dout = host ? s.out : out;
+  const int64_t dstride = host ? 1 : out_stride;
+  const hipError_t e =
+      f32 ? pfe::launch_pfd_avgprof_f32(xf, E, proflen, n, s.csum, dout, dstride, h->stream)
+          : pfe::launch_pfd_avgprof(xd, E, proflen, n, s.csum, dout, dstride, h->stream);
+  if (e != hipSuccess)
+    return set_err(h, PFE_EDEVICE, "pfd_avgprof launch: %s", hipGetErrorString(e));
+  if (host) {
+    // the n values as one block, then to their places among the caller's doubles
+    std::vector<double> dense;
+    double* dst = out;
+    if (out_stride > 1) {
+      dense.resize((size_t)n);
+      dst = dense.data();
+    }
+    if ((rc = fetch(h, dst, dout, (size_t)n))) return rc;
+    PFE_HIP(h, hipStreamSynchronize(h->stream));
+    if (out_stride > 1)
+      for (int64_t i = 0; i < n; ++i) out[i * out_stride] = dense[(size_t)i];
+  }
+  return call_end(h);
+}
+
+int pfe_pfd_avgprof(pfe_handle* h, const double* profs, int32_t npart, int32_t nsub,
+                    int32_t proflen, int64_t n, double* out, int64_t out_stride, uint32_t flags) {
+  return pfd_avgprof_call(h, profs, nullptr, false, npart, nsub, proflen, n, out, out_stride, flags);
+}
+
+int pfe_pfd_avgprof_f32(pfe_handle* h, const float* profs, int32_t npart, int32_t nsub,
+                        int32_t proflen, int64_t n, double* out, int64_t out_stride,
+                        uint32_t flags) {
+  return pfd_avgprof_call(h, nullptr, profs, true, npart, nsub, proflen, n, out, out_stride, flags);
 }
 
 int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* chis,
@@ -1114,12 +1208,14 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   pfe::PfdArgs a = pfd_args(h, in);
   const bool all = groups == pfe::PFD_G_ALL;
   const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
+  // only the chi^2 sweep reads the average: a call without it has nothing to derive
+  const bool derive = (flags & PFE_FLAG_PFD_AVGPROF) && (groups & pfe::PFD_G_DM);
   const int cus = pfe::device_cus();
   // the scratch with the chain's workspace laid out for a pass of cn folds
   auto walk = [&](int64_t cn) {
     return [&, cn](pfe::Arena& A) {
       return pfe::pfd_scores_layout(A, *in, host, groups, k, plan(cn).bytes(), cus, h->opt,
-                                    f32 ? pass : 0, cn);
+                                    f32 ? pass : 0, cn, derive);
     };
   };
   if (n % pass) {  // a shorter last pass: its layout fits as well
@@ -1130,6 +1226,8 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   pfe::PfdScoresStage s;
   rc = lay_out(h, s, walk(pass));
   if (rc || (host && (rc = stage_pfd(h, in, x32, s.in, a)))) return rc;
+  double* wscal = nullptr;
+  if (derive && (rc = pfd_avg_begin(h, in, host ? s.in.scal : nullptr, s.avg, a, wscal))) return rc;
   double* dout = host ? s.out : out;
   uint32_t* dstat = host ? s.status : status;
   for (int64_t f0 = 0; f0 < n; f0 += pass) {
@@ -1139,6 +1237,7 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
       s = walk(cn)(place);
     }
     pfe::PfdArgs b;
+    if (derive && (rc = pfd_avg_pass(h, fn, a, x32, f0, cn, s.avg.csum, wscal))) return rc;
     if ((rc = pfd_pass(h, fn, a, x32, s.in.psum, f0, cn, b))) return rc;
     // a group call scores into a 22-column scratch of its own
     double* d22 = all ? dout + f0 * 22 : s.d22;

@@ -351,6 +351,53 @@ inline int64_t pfd_f32_chunk(int nsub, int L, int64_t n, int64_t opt) {
 hipError_t launch_pfd_partsum_f32(const float* x, double* s, int npart, int nsub, int L, int64_t n,
                                   hipStream_t st);
 
+// ---- a fold's average: pfe_pfd_avgprof and PFE_FLAG_PFD_AVGPROF (pfd_avgprof.hip) --------
+// numpy's (profs / proflen).sum() of each fold: k_pfd_avgprof sums every chunk of
+// PFD_AVG_CHUNK values (numpy's reduction buffer) of a fold's E = npart x nsub x proflen into
+// csum (n x pfd_avg_chunks(E) doubles), k_pfd_avgprof_fin adds a fold's chunk sums in order
+// into out[i * stride]
+constexpr int PFD_AVG_CHUNK = 8192;
+inline int64_t pfd_avg_chunks(int64_t E) { return (E + PFD_AVG_CHUNK - 1) / PFD_AVG_CHUNK; }
+hipError_t launch_pfd_avgprof(const double* x, int64_t E, int L, int64_t n, double* csum,
+                              double* out, int64_t stride, hipStream_t st);
+hipError_t launch_pfd_avgprof_f32(const float* x, int64_t E, int L, int64_t n, double* csum,
+                                  double* out, int64_t stride, hipStream_t st);
+
+// pfe_pfd_avgprof / pfe_pfd_avgprof_f32: a host-pointer call stages the cube (as the values it
+// holds) and its n results; the chunk sums follow
+struct PfdAvgStage {
+  double* profs = nullptr;
+  float* profs32 = nullptr;
+  double *out = nullptr, *csum = nullptr;
+};
+inline PfdAvgStage pfd_avgprof_layout(Arena& A, int64_t E, int64_t n, bool host, bool f32) {
+  PfdAvgStage s;
+  if (host) {
+    if (f32)
+      s.profs32 = A.take<float>((size_t)n * E, "profs32");
+    else
+      s.profs = A.take<double>((size_t)n * E, "profs");
+    s.out = A.take<double>((size_t)n, "out");
+  }
+  s.csum = A.take<double>((size_t)n * pfd_avg_chunks(E), "avg_csum");
+  return s;
+}
+
+// PFE_FLAG_PFD_AVGPROF on a PFD call: the chunk sums of the `folds` folds one pass derives
+// (all n of an f64 call), and -- device pointers, whose scal is the caller's and is never
+// written -- a copy of scal for the derived values (a host-pointer call writes into its
+// staged scal)
+struct PfdAvgWork {
+  double *csum = nullptr, *scal = nullptr;
+};
+inline PfdAvgWork pfd_avg_work_layout(Arena& A, const pfe_pfd_in& in, bool host, int64_t folds) {
+  PfdAvgWork w;
+  const int64_t E = (int64_t)in.npart * in.nsub * in.proflen;
+  w.csum = A.take<double>((size_t)folds * pfd_avg_chunks(E), "avg_csum");
+  if (!host) w.scal = A.take<double>((size_t)in.n * PFE_PFD_NSCAL, "avg_scal");
+  return w;
+}
+
 // the three inputs every PFD call stages.  A float32 call (f32_chunk > 0: its folds per pass)
 // stages the cube as the floats it is (profs32, no profs), and -- host pointers or device --
 // takes psum behind its staged arrays
@@ -377,9 +424,10 @@ inline double* pfd_psum_layout(Arena& A, const pfe_pfd_in& in, int64_t f32_chunk
 // pfe_pfd_dmprof: the outputs the caller asked for, then ws_bytes for the two part-sum
 // buffers of the split pipeline or the slabs of the global-memory kernel (PfdGlobalPlan).
 // pfe_pfd_dmprof_f32 (f32_chunk > 0): the same with the float cube and psum; ws_bytes is
-// then what one pass needs
+// then what one pass needs.  avgprof (PFE_FLAG_PFD_AVGPROF): pfd_avg_work_layout behind psum
 struct PfdDmprofStage {
   PfdInputs in;
+  PfdAvgWork avg;
   double* profile = nullptr;
   float* chis = nullptr;
   double* lyon8 = nullptr;
@@ -388,7 +436,7 @@ struct PfdDmprofStage {
 };
 inline PfdDmprofStage pfd_dmprof_layout(Arena& A, const pfe_pfd_in& in, bool host, bool profile,
                                         bool chis, bool lyon8, size_t ws_bytes,
-                                        int64_t f32_chunk = 0) {
+                                        int64_t f32_chunk = 0, bool avgprof = false) {
   PfdDmprofStage s;
   const size_t n = (size_t)in.n;
   if (host) {
@@ -399,6 +447,7 @@ inline PfdDmprofStage pfd_dmprof_layout(Arena& A, const pfe_pfd_in& in, bool hos
     s.status = A.take<uint32_t>(n, "status");
   }
   if (f32_chunk > 0) s.in.psum = pfd_psum_layout(A, in, f32_chunk);
+  if (avgprof) s.avg = pfd_avg_work_layout(A, in, host, f32_chunk > 0 ? f32_chunk : in.n);
   if (ws_bytes) s.ws = A.take<char>(ws_bytes, "ws");
   return s;
 }
@@ -408,9 +457,12 @@ inline PfdDmprofStage pfd_dmprof_layout(Arena& A, const pfe_pfd_in& in, bool hos
 // global-memory kernel (0: the fold lives in LDS).  The float32 forms (f32_chunk > 0): the
 // float cube and psum, and d22, the chain's workspace and g_bytes for the `pass` folds of one
 // pass (a pass's chain then works on what the f64 call on that many folds lays out); the
-// staged arrays and psum come first, so they stay put from one pass to the next
+// staged arrays and psum come first, so they stay put from one pass to the next.  avgprof
+// (PFE_FLAG_PFD_AVGPROF on a call that reads the average): pfd_avg_work_layout behind psum,
+// sized by f32_chunk, so it stays put as well
 struct PfdScoresStage {
   PfdInputs in;
+  PfdAvgWork avg;
   double *out = nullptr, *d22 = nullptr;
   uint32_t* status = nullptr;
   Pfd22Work work;
@@ -419,7 +471,7 @@ struct PfdScoresStage {
 inline PfdScoresStage pfd_scores_layout(Arena& A, const pfe_pfd_in& in, bool host,
                                         unsigned groups, int k, size_t g_bytes, int cus,
                                         const Options& o, int64_t f32_chunk = 0,
-                                        int64_t pass = 0) {
+                                        int64_t pass = 0, bool avgprof = false) {
   PfdScoresStage s;
   const size_t n = (size_t)in.n;
   const int64_t wn = f32_chunk > 0 ? pass : in.n;
@@ -429,6 +481,7 @@ inline PfdScoresStage pfd_scores_layout(Arena& A, const pfe_pfd_in& in, bool hos
     s.status = A.take<uint32_t>(n, "status");
   }
   if (f32_chunk > 0) s.in.psum = pfd_psum_layout(A, in, f32_chunk);
+  if (avgprof) s.avg = pfd_avg_work_layout(A, in, host, f32_chunk > 0 ? f32_chunk : in.n);
   if (groups != PFD_G_ALL) s.d22 = A.take<double>((size_t)wn * 22, "d22");
   s.work = pfd22_layout(A, wn, in.proflen, groups, cus, o);
   if (g_bytes) s.tg = A.take<char>(g_bytes, "tg");

@@ -1,0 +1,221 @@
+// pfd_avgprof.hip — a fold's average on gfx950: numpy's (profs / proflen).sum() of the cube.
+//
+// PFDFile.load keeps avgprof = (self.profs / self.proflen).sum() (PFDFile.py:225), and the
+// chi^2-vs-DM sweep subtracts it from every bin, so the DM curve wants its exact bits.  numpy
+// evaluates the expression as
+//   y[e] = (double)x[e] / (double)proflen            the correctly rounded fp64 quotient
+//   c[k] = pairwise sum of y[8192 k .. 8192 k + 8191]  (the last chunk shorter)
+//   sum  = 0.0 + c[0] + c[1] + c[2] + ...              in order, onto numpy's initial 0.0
+// where a pairwise sum splits n > 128 values at floor8(n / 2) and sums a leaf of n <= 128 in
+// eight accumulators, r[t] = y[t] + y[t + 8] + ..., ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then
+// the n % 8 last values in order (n < 8: 0.0 + y0 + y1 ...).  This is not one pairwise tree
+// over the cube: the chunks of 8192 are numpy's reduction buffers.  The initial 0.0 shows in
+// one case only: a fold whose values are all -0.0 sums to +0.0, as numpy's does.
+//
+// k_pfd_avgprof: one wave per (fold, chunk).  Its eight 8-lane groups each take one leaf of
+// the chunk's tree at a time, lane t of a group being accumulator t (np_sum.h's layout), so a
+// group's load is 8 consecutive values and the 16 loads of a lane walk the leaf's 1 KiB; the
+// leaf sums meet in LDS and are added up the tree.  k_pfd_avgprof_fin: one lane per fold adds
+// the fold's chunk sums in order.  Two plain kernels on one stream; no atomics.
+#include <hip/hip_runtime.h>
+
+#include "launch.h"
+#include "np_sum.h"
+
+namespace pfe {
+
+#pragma clang fp contract(off)
+
+static_assert(PFD_AVG_CHUNK == NP_BUFSIZE, "a chunk is one of numpy's reduction buffers");
+
+constexpr int AVG_WPB = 4;        // waves per block (each works alone: no block barrier)
+// a node is split only when it holds > 128 values, into floor8(n/2) >= 64 and the rest, so a
+// leaf of a split chunk holds >= 64 values: <= 128 leaves, and (np_inl_max(7) >= 8192) every
+// leaf at depth <= 7
+constexpr int AVG_MAX_LEAVES = PFD_AVG_CHUNK / 64;
+constexpr int AVG_STACK = 10;     // depth of the two walks of a chunk's tree (<= 8 needed)
+
+// a node of a chunk's tree: off < 8192 (13 bits), len <= 8192 (14 bits), depth <= 7
+__device__ __forceinline__ uint32_t avg_node(int off, int len, int depth) {
+  return (uint32_t)off | ((uint32_t)len << 13) | ((uint32_t)depth << 27);
+}
+__device__ __forceinline__ int avg_off(uint32_t v) { return (int)(v & 8191u); }
+__device__ __forceinline__ int avg_len(uint32_t v) { return (int)((v >> 13) & 16383u); }
+__device__ __forceinline__ int avg_depth(uint32_t v) { return (int)(v >> 27); }
+
+// x / L.  P2 (L a power of two): x * (1 / L), the same real number rounded once, so the same
+// bits (subnormal results included); else the IEEE quotient
+template <bool P2>
+__device__ __forceinline__ double avg_scale(double x, double dl, double inv) {
+  if constexpr (P2) return x * inv;
+  return x / dl;
+}
+
+// numpy's leaf sum of p[0 .. len), 8 <= len <= 128, scaled: the result in every lane of the
+// 8-lane group (t = lane & 7).  Every lane of the wave is here (the DPP steps read within a
+// group), groups may hold leaves of different lengths: selects, no divergent branch.
+template <typename T, bool P2>
+__device__ __forceinline__ double avg_leaf(const T* p, int len, int t, double dl, double inv) {
+  const int nb = len & ~7;
+  T raw[16];
+#pragma unroll
+  for (int m = 0; m < 16; ++m) raw[m] = p[min(t + 8 * m, len - 1)];
+  double r = avg_scale<P2>((double)raw[0], dl, inv);
+#pragma unroll
+  for (int m = 1; m < 16; ++m) {
+    const double y = avg_scale<P2>((double)raw[m], dl, inv);
+    r = 8 * m < nb ? r + y : r;
+  }
+  r += dpp_f64<DPP_QUAD_XOR1>(r);  // ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7))
+  r += dpp_f64<DPP_QUAD_XOR2>(r);
+  r += dpp_f64<DPP_ROW_HALF_MIRROR>(r);
+  for (int k = 0; k < 7; ++k) {  // the len % 8 last values, in order
+    const bool more = nb + k < len;
+    if (__ballot(more) == 0) break;
+    const double y = avg_scale<P2>((double)p[min(nb + k, len - 1)], dl, inv);
+    r = more ? r + y : r;
+  }
+  return r;
+}
+
+// csum[fold * nch + chunk] = numpy's pairwise sum of the chunk's scaled values.  X: n folds of
+// E values, dense; nch = ceil(E / 8192); total = n * nch waves.
+template <typename T, bool P2>
+__global__ __launch_bounds__(AVG_WPB * 64) void k_pfd_avgprof(const T* __restrict__ X, int64_t E,
+                                                             int nch, int64_t total, double dl,
+                                                             double inv,
+                                                             double* __restrict__ csum) {
+  __shared__ double s_sum[AVG_WPB][AVG_MAX_LEAVES];
+  __shared__ uint32_t s_tab[AVG_WPB][AVG_MAX_LEAVES];
+  __shared__ uint32_t s_walk[AVG_WPB][AVG_STACK];
+  __shared__ double s_val[AVG_WPB][AVG_STACK];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t wg = (int64_t)blockIdx.x * AVG_WPB + w;
+  if (wg >= total) return;  // the whole wave
+  const int64_t fold = wg / nch;
+  const int ch = (int)(wg - fold * nch);
+  const int64_t e0 = (int64_t)ch * PFD_AVG_CHUNK;
+  const int n = (int)(E - e0 < PFD_AVG_CHUNK ? E - e0 : PFD_AVG_CHUNK);
+  const T* x = X + fold * E + e0;
+
+  if (n < 8) {  // 0.0 + y0 + y1 ...
+    double r = 0.0;
+    for (int i = 0; i < n; ++i) r += avg_scale<P2>((double)x[i], dl, inv);
+    if (lane == 0) csum[wg] = r;
+    return;
+  }
+
+  // the leaves of the chunk's tree, in order: one (n <= 128), 64 of 128 values under six
+  // full levels (n = 8192), or what a walk of the tree by lane 0 finds
+  const bool full = n == PFD_AVG_CHUNK, one = n <= 128;
+  int nleaf = one ? 1 : AVG_MAX_LEAVES / 2;
+  if (!full && !one) {
+    if (lane == 0) {
+      int sp = 1, cnt = 0;
+      s_walk[w][0] = avg_node(0, n, 0);
+      while (sp > 0) {
+        const uint32_t v = s_walk[w][--sp];
+        const int off = avg_off(v), len = avg_len(v), d = avg_depth(v);
+        if (len <= 128) {
+          s_tab[w][cnt++] = v;
+        } else {
+          int n2 = len / 2;
+          n2 -= n2 % 8;
+          s_walk[w][sp++] = avg_node(off + n2, len - n2, d + 1);  // the right half waits
+          s_walk[w][sp++] = avg_node(off, n2, d + 1);
+        }
+      }
+      s_walk[w][0] = (uint32_t)cnt;
+    }
+    lds_sync();
+    nleaf = uni((int)s_walk[w][0]);
+  }
+
+  const int g = lane >> 3, t = lane & 7;
+  for (int b = 0; b < nleaf; b += 8) {
+    const int j = min(b + g, nleaf - 1);  // a group past the last leaf sums it again, unstored
+    int off = 0, len = n;
+    if (full) {
+      off = 128 * j;
+      len = 128;
+    } else if (!one) {
+      const uint32_t v = s_tab[w][j];
+      off = avg_off(v);
+      len = avg_len(v);
+    }
+    const double s = avg_leaf<T, P2>(x + off, len, t, dl, inv);
+    if (t == 0 && b + g < nleaf) s_sum[w][b + g] = s;
+  }
+  lds_sync();
+
+  if (one) {
+    if (lane == 0) csum[wg] = s_sum[w][0];
+  } else if (full) {
+    // six full levels over 64 leaves in order: the xor butterfly (a + b = b + a bit for bit)
+    double v = s_sum[w][lane];
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) v += __shfl_xor(v, s);
+    if (lane == 0) csum[wg] = v;
+  } else if (lane == 0) {
+    // the leaves in order with their depths: two neighbours of one depth are the halves of a
+    // node, left + right
+    int sp = 0;
+    for (int j = 0; j < nleaf; ++j) {
+      double val = s_sum[w][j];
+      int d = avg_depth(s_tab[w][j]);
+      while (sp > 0 && (int)s_walk[w][sp - 1] == d) {
+        val = s_val[w][--sp] + val;
+        --d;
+      }
+      s_val[w][sp] = val;
+      s_walk[w][sp++] = (uint32_t)d;
+    }
+    csum[wg] = s_val[w][0];
+  }
+}
+
+// out[i * stride] = 0.0 + c[i][0] + c[i][1] + ... + c[i][nch - 1], in order
+__global__ __launch_bounds__(256) void k_pfd_avgprof_fin(const double* __restrict__ csum, int nch,
+                                                         int64_t n, double* __restrict__ out,
+                                                         int64_t stride) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double* c = csum + i * nch;
+  double r = 0.0;
+  for (int k = 0; k < nch; ++k) r += c[k];
+  out[i * stride] = r;
+}
+
+template <typename T>
+static hipError_t launch_avgprof(const T* x, int64_t E, int L, int64_t n, double* csum, double* out,
+                                 int64_t stride, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const int64_t nch = pfd_avg_chunks(E), total = n * nch;
+  const int64_t blocks = (total + AVG_WPB - 1) / AVG_WPB;
+  if (E < 1 || L < 1 || nch > 0x7fffffff || blocks > 0x7fffffff) return hipErrorInvalidValue;
+  const bool p2 = (L & (L - 1)) == 0;
+  const double dl = (double)L, inv = 1.0 / dl;  // exact for a power of two
+  const dim3 grid((unsigned)blocks), block(AVG_WPB * 64);
+  if (p2)
+    hipLaunchKernelGGL((k_pfd_avgprof<T, true>), grid, block, 0, st, x, E, (int)nch, total, dl, inv,
+                       csum);
+  else
+    hipLaunchKernelGGL((k_pfd_avgprof<T, false>), grid, block, 0, st, x, E, (int)nch, total, dl,
+                       inv, csum);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_pfd_avgprof_fin, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, csum,
+                     (int)nch, n, out, stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_pfd_avgprof(const double* x, int64_t E, int L, int64_t n, double* csum,
+                              double* out, int64_t stride, hipStream_t st) {
+  return launch_avgprof(x, E, L, n, csum, out, stride, st);
+}
+hipError_t launch_pfd_avgprof_f32(const float* x, int64_t E, int L, int64_t n, double* csum,
+                                  double* out, int64_t stride, hipStream_t st) {
+  return launch_avgprof(x, E, L, n, csum, out, stride, st);
+}
+
+}  // namespace pfe

@@ -27,7 +27,10 @@ class PFDData:
         self.__dict__.update(kw)
 
 
-def read(path: str) -> PFDData:
+def read(path: str, avgprof: bool = True) -> PFDData:
+    """One .pfd file.  avgprof False: the pass over the cube for (profs / proflen).sum() is
+    left out and the attribute is None (the PFD calls derive it on the device:
+    Engine.pfd_dmprof(..., derive_avgprof=True))."""
     with open(path, "rb") as f:
         data = f.read()
     pos = 0
@@ -109,7 +112,7 @@ def read(path: str) -> PFDData:
         chan_wid=chan_wid, bestdm=bestdm, topo_p1=vals["topo"][1], bary_p1=vals["bary"][1],
         fold_p1=vals["fold"][1], orb=orb, dms=dms, periods=periods, pdots=pdots, profs=profs,
         stats=stats, binspersec=binspersec, chanpersub=chanpersub, subdeltafreq=subdeltafreq,
-        losubfreq=losubfreq, subfreqs=subfreqs, avgprof=(profs / proflen).sum(),
+        losubfreq=losubfreq, subfreqs=subfreqs, avgprof=(profs / proflen).sum() if avgprof else None,
         varprof=varprof)
 
 
@@ -153,7 +156,9 @@ def write(path: str, *, profs, stats=None, dms, bestdm, fold_p1, bary_p1=None, l
 
 
 def batch_inputs(datas):
-    """Dense pfe_pfd_dmprof inputs for PFDData of one (npart, nsub, proflen) shape."""
+    """Dense pfe_pfd_dmprof inputs for PFDData of one (npart, nsub, proflen) shape.  A fold
+    read without its average (avgprof None) gets NaN in scal[:, 2]: score it with
+    derive_avgprof=True."""
     n = len(datas)
     d0 = datas[0]
     profs = np.empty((n, d0.npart, d0.nsub, d0.proflen), dtype=np.float64)
@@ -163,6 +168,6 @@ def batch_inputs(datas):
         profs[i] = d.profs
         subfreqs[i] = d.subfreqs
         dms = np.atleast_1d(d.dms)
-        scal[i] = (d.bestdm, d.binspersec, d.avgprof, d.varprof, dms[0], dms[-1], d.numdms,
-                   d.bary_p1)
+        avg = np.nan if d.avgprof is None else d.avgprof
+        scal[i] = (d.bestdm, d.binspersec, avg, d.varprof, dms[0], dms[-1], d.numdms, d.bary_p1)
     return profs, subfreqs, scal

@@ -241,9 +241,26 @@ def is_pfd(path: str) -> bool:
 
 def _read_pfd(path):
     try:
-        return _pfd.read(path), None
+        # without the pass over the cube for avgprof: _pfd_call has the device derive it
+        return _pfd.read(path, avgprof=False), None
     except Exception as e:  # the reference logs and skips unreadable candidates
         return None, f"{type(e).__name__}: {e}"
+
+
+def _pfd_call(engine, fn, datas, **kw):
+    """engine.<fn> on the packed folds.  libpfe derives every fold's average from the cube on
+    the device (derive_avgprof: scal[:, 2] is not read, so folds read with avgprof=False need
+    no pass over the cube here); any other engine gets scal complete, a missing average
+    filled in as PFDFile.load computes it."""
+    from ._native import Engine
+
+    if isinstance(engine, Engine):
+        kw["derive_avgprof"] = True
+    else:
+        for d in datas:
+            if d.avgprof is None:
+                d.avgprof = (d.profs / d.proflen).sum()
+    return getattr(engine, fn)(*_pfd.batch_inputs(datas), **kw)
 
 
 def score_pfd(datas, engine=None, batch: int = 1 << 14):
@@ -260,9 +277,8 @@ def score_pfd(datas, engine=None, batch: int = 1 << 14):
     for _shape, idx in groups.items():
         for s0 in range(0, len(idx), batch):
             part = idx[s0:s0 + batch]
-            profs, subfreqs, scal = _pfd.batch_inputs([datas[i] for i in part])
             try:
-                r = engine.pfd_dmprof(profs, subfreqs, scal, chis=False)
+                r = _pfd_call(engine, "pfd_dmprof", [datas[i] for i in part], chis=False)
             except PfeError as e:  # a shape the library refuses fails its folds, not the run
                 for i in part:
                     err[i] = f"Exception: {e}"
@@ -290,7 +306,7 @@ def score_pfd22(datas, engine=None, batch: int = 1 << 16):
         for s0 in range(0, len(idx), batch):
             part = idx[s0:s0 + batch]
             try:
-                o, st = engine.pfd_bates22(*_pfd.batch_inputs([datas[i] for i in part]))
+                o, st = _pfd_call(engine, "pfd_bates22", [datas[i] for i in part])
             except PfeError as e:  # a shape the library refuses fails its folds, not the run
                 for i in part:
                     err[i] = f"Exception: {e}"
@@ -318,7 +334,7 @@ def pfd_profile_and_curve(datas, engine=None, batch: int = 1 << 14):
         for s0 in range(0, len(idx), batch):
             part = idx[s0:s0 + batch]
             try:
-                r = engine.pfd_dmprof(*_pfd.batch_inputs([datas[i] for i in part]), lyon8=False)
+                r = _pfd_call(engine, "pfd_dmprof", [datas[i] for i in part], lyon8=False)
             except PfeError as e:  # a shape the library refuses fails its folds, not the run
                 for i in part:
                     err[i] = f"Exception: {e}"

@@ -55,6 +55,7 @@ extern "C" {
 /* flags */
 #define PFE_FLAG_DEVICE_PTRS 0x1u /* all array arguments are device pointers */
 /* PFE_FLAG_PFD_AVGPROF 0x2u: the PFD calls only; defined with pfe_pfd_avgprof below */
+/* PFE_FLAG_PFD_BSWAP 0x4u: the f64 PFD calls only; defined with pfe_pfd_avgprof below */
 
 /* Per-candidate status bits (pfe_bates22).  A non-zero status means the reference would
  * have raised inside Candidate.calculateScores and DataProcessor would have logged the
@@ -142,7 +143,8 @@ int pfe_synchronize(pfe_handle* h);
  *                        sub-bands fit the LDS stay on chip and every other shape goes through
  *                        per-wave slabs of the handle's scratch; 1 = every shape through the
  *                        slabs (same bits)
- *   PFE_OPT_PFD_F32_CHUNK  the pfe_pfd_*_f32 calls: folds per pass, >= 0.  0 (default) = as many
+ *   PFE_OPT_PFD_F32_CHUNK  the pfe_pfd_*_f32 calls, and the f64 PFD calls under
+ *                        PFE_FLAG_PFD_BSWAP: folds per pass, >= 0.  0 (default) = as many
  *                        folds as keep a pass's part sums (nsub x proflen doubles a fold)
  *                        within 1 GiB; a larger value is cut to that, and to n (same bits)
  * Returns PFE_EINVAL for an unknown option or an out-of-range value.
@@ -504,6 +506,39 @@ int pfe_pfd_subband3_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, u
  * and their _f32 forms do not read the average: they accept the flag and do no extra work.
  * Without the flag every call does what it did before. */
 #define PFE_FLAG_PFD_AVGPROF 0x2u /* PFD calls: derive scal[PFE_PFD_AVGPROF] from the cube */
+
+/* ---- cubes in the opposite byte order ----------------------------------------------------
+ * A .pfd file written on a big-endian machine holds every double of its cube byte-reversed.
+ * PFE_FLAG_PFD_BSWAP, on the five f64 PFD calls (pfe_pfd_dmprof, _bates22, _params4, _dmfit4,
+ * _subband3) and on pfe_pfd_avgprof: profs holds 8-byte values whose bytes are reversed, as
+ * such a file holds them; the file's cube bytes go to the device untouched (pfe_pfd_pack,
+ * pfe_io.h) and the byte order is dealt with where each value is loaded.  subfreqs, scal and
+ * every output stay native.
+ *
+ * Contract: every output of a flagged call is, bit for bit, the output of the unflagged call on
+ * the cube with every 8-byte value byte-reversed (numpy's cube.byteswap()), with the same
+ * subfreqs, scal, options and other flags.  NaN payloads, signed zeros, infinities and
+ * subnormals are carried through.  Nothing in memory is rewritten: the caller's cube is never
+ * written to, and no swapped copy of the whole cube is made.  One case is outside it: where
+ * two NaNs of different payloads meet in the sum of one element's parts, the payload of the
+ * earlier part survives here, while the unflagged call keeps the one its kernel's add holds in
+ * its first operand (the later part's on the four-wave route, the earlier one's on the split
+ * pipeline: the f64 routes do not agree among themselves).  The result is a NaN either way.
+ *
+ * How: the float32 path with 8-byte words.  A part-sum kernel reads the raw words, reverses
+ * them in registers and forms S[e] = X[0][e] + X[1][e] + ... + X[npart-1][e] in fp64, from the
+ * value of part 0, in the order the f64 kernels sum the parts of an element in; the f64 kernels
+ * run on S as folds of one part.  16-byte loads when nsub x proflen is even and profs is
+ * 16-byte aligned, 8-byte loads otherwise (profs 8-byte aligned as ever); same bits.  The
+ * average (pfe_pfd_avgprof, and PFE_FLAG_PFD_AVGPROF together with this flag, pass by pass) is
+ * taken by the same kernels with each word widened to double through the reversal.
+ * Scratch: passes of `chunk` folds by the rule of the float32 calls -- chunk = min(n, max(1,
+ * 2^30 / (8 x nsub x proflen))), or PFE_OPT_PFD_F32_CHUNK when that is smaller (the option
+ * governs both paths) -- and, behind the arrays a host-pointer call stages (the cube as the
+ * words it holds), chunk x nsub x proflen doubles of part sums, then the scratch of the f64
+ * call on `chunk` folds.
+ * The _f32 calls refuse the flag with PFE_EINVAL.  Without the flag nothing changes. */
+#define PFE_FLAG_PFD_BSWAP 0x4u /* f64 PFD calls: profs holds byte-reversed 8-byte values */
 
 int pfe_pfd_avgprof(pfe_handle* h, const double* profs, int32_t npart, int32_t nsub,
                     int32_t proflen, int64_t n, double* out, int64_t out_stride, uint32_t flags);

@@ -99,6 +99,92 @@ int pfe_format_rows(const char* name_blob, const int64_t* name_off, const double
                     const uint8_t* skip, int32_t nthreads, char* buf, int64_t cap,
                     int64_t* len);
 
+/* ---- PRESTO .pfd files: native reader and cube packer (csrc/pfd_io.cpp) --------------------
+ * Replaces, on the batched product path, the per-file Python reader (pfd.read, which follows
+ * PFDFile.py:96-252): a pool of host threads parses each file's header exactly as pfd.read does
+ *   - the byte-order test on the first five ints (big-endian when one exceeds 100000 in
+ *     magnitude read little-endian, PFDFile.py:113-118),
+ *   - seven more ints, the four length-prefixed strings, the optional 16+16-byte RA/Dec block
+ *     (present when the next 16 bytes are all in "0123456789:.-\0"), the fold's doubles and
+ *     floats, dms / periods / pdots,
+ * records where the cube (npart x nsub x proflen doubles) and the foldstats (npart x nsub x 7
+ * doubles) lie in the file, reads the foldstats and sums prof_var (column 5) in the reference's
+ * order (part-major, then sub, sequentially from 0.0).  The cube is not read by the scan:
+ * pfe_pfd_pack brings it from the file into the caller's slab by pread, untouched -- no value
+ * is converted, copied twice or byte-swapped on the host; a big-endian file's cube goes to the
+ * PFD calls as it is, under PFE_FLAG_PFD_BSWAP (pfe.h).
+ * A file the native reader cannot reproduce exactly gets a non-zero status; the host then
+ * falls back to pfd.read for that file alone, which raises what it always raised:
+ *   PFE_IO_ERR_OPEN    cannot open / stat / read the file (OSError)
+ *   PFE_IO_ERR_HEADER  the file ends inside the header, an empty file included (struct.error)
+ *   PFE_IO_ERR_CUBE    a big-endian file ends inside the cube (struct.error; a little-endian
+ *                      one does not fail: every row that is not complete reads as zeros)
+ *   PFE_IO_ERR_VALUE   a header count the reader does not take on: numdms < 1, npart / nsub /
+ *                      proflen < 1, a negative length, a cube beyond 2^50 bytes */
+#define PFE_IO_ERR_HEADER 7
+#define PFE_IO_ERR_CUBE 8
+
+/* fields for pfe_pfd_fetch; every value in native byte order */
+#define PFE_PFD_F_DMS 0      /* double[numdms] */
+#define PFE_PFD_F_PERIODS 1  /* double[numperiods] */
+#define PFE_PFD_F_PDOTS 2    /* double[numpdots] */
+#define PFE_PFD_F_STATS 3    /* double[npart*nsub*7], read from the file again; zeros where absent */
+#define PFE_PFD_F_SUBFREQS 4 /* double[nsub] = arange(nsub) * subdeltafreq + losubfreq */
+/* double[PFE_PFD_NHEAD]: dt, startT, endT, tepoch, bepoch, avgvoverc, lofreq, chan_wid, bestdm,
+   topo_p1, bary_p1, fold_p1, orb[0..6], binspersec, subdeltafreq, losubfreq, varprof */
+#define PFE_PFD_F_HEAD 5
+#define PFE_PFD_NHEAD 23
+#define PFE_PFD_F_FILENM 6   /* char[slen[0]] */
+#define PFE_PFD_F_CANDNM 7   /* char[slen[1]] */
+#define PFE_PFD_F_TELESCOPE 8 /* char[slen[2]] */
+#define PFE_PFD_F_PGDEV 9    /* char[slen[3]] */
+#define PFE_PFD_F_RASTR 10   /* char[slen[4]] ("Unknown" without the RA/Dec block) */
+#define PFE_PFD_F_DECSTR 11  /* char[slen[5]] */
+
+typedef struct {
+  int32_t status;     /* PFE_IO_* */
+  int32_t big_endian; /* 1: the file's values are byte-reversed on this (little-endian) host */
+  int32_t npart, nsub, proflen;
+  int32_t numdms, numperiods, numpdots;
+  int32_t numchan;
+  int32_t chanpersub; /* numchan // nsub (floor) */
+  int32_t has_posn;   /* the RA/Dec block is there */
+  int32_t slen[6];    /* lengths of the six strings (PFE_PFD_F_FILENM ...) */
+  int32_t reserved;
+  int64_t rows;       /* complete cube rows (proflen values each) in the file, <= npart * nsub */
+  int64_t stat_rows;  /* complete foldstats records (7 doubles) in the file, <= npart * nsub */
+  int64_t cube_off;   /* file offset of the cube */
+  int64_t stats_off;  /* file offset of the foldstats (meaningful when stat_rows > 0) */
+  /* PFE_PFD_NSCAL layout of pfe_pfd_in.scal: bestdm, fold_p1 * proflen, NaN (the average:
+     PFE_FLAG_PFD_AVGPROF derives it on the device), varprof, dms[0], dms[numdms-1], numdms,
+     bary_p1 */
+  double scal[8];
+} pfe_pfd_info;
+
+typedef struct pfe_pfd_batch pfe_pfd_batch;
+
+/* Scan n files with nthreads host threads (<= 0: the hardware threads, 16 at the most -- a
+   shared machine's other cores are not this call's).  Returns PFE_OK or PFE_EINVAL; per-file
+   problems are reported in the file's info.status. */
+int pfe_pfd_scan(const char* const* paths, int64_t n, int32_t nthreads, pfe_pfd_batch** out);
+int64_t pfe_pfd_count(const pfe_pfd_batch* b);
+/* Every file's info: out[0 .. count) (capacity >= pfe_pfd_count(b), else PFE_EINVAL). */
+int pfe_pfd_info_all(const pfe_pfd_batch* b, pfe_pfd_info* out, int64_t capacity);
+/* copy one field of file i into dst (capacity in elements, which must be the field's length
+   exactly); PFE_EINVAL if it is not, the file failed, or (PFE_PFD_F_STATS) it cannot be read */
+int pfe_pfd_fetch(const pfe_pfd_batch* b, int64_t i, int32_t field, void* dst, int64_t capacity);
+/* Rows (file indices) into dense, caller-owned arrays for the PFD calls of pfe.h:
+   profs_raw[nrows][npart*nsub*proflen] 8-byte words -- the file's cube bytes, by pread straight
+   into row r, in the file's byte order (big-endian rows: score with PFE_FLAG_PFD_BSWAP); a
+   little-endian file whose cube is cut short gets zeros for every row that is not complete;
+   subfreqs[nrows][nsub] and scal[nrows][8], native (scal[2], the average, NaN: score with
+   PFE_FLAG_PFD_AVGPROF).  Any output may be NULL.  All rows of one pack are scanned files
+   (status 0) of one shape and one byte order, else PFE_EINVAL; PFE_EINVAL too when a file no
+   longer holds what the scan saw.  nthreads as pfe_pfd_scan. */
+int pfe_pfd_pack(const pfe_pfd_batch* b, const int64_t* rows, int64_t nrows, int32_t nthreads,
+                 void* profs_raw, double* subfreqs, double* scal);
+void pfe_pfd_free(pfe_pfd_batch* b);
+
 #ifdef __cplusplus
 }
 #endif

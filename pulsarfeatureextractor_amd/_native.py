@@ -70,6 +70,7 @@ EXPORTED_SYMBOLS = (
     "pfe_pfd_avgprof_f32",
 )
 PFE_FLAG_PFD_AVGPROF = 0x2  # PFD calls: derive scal[:, PFE_PFD_AVGPROF] from the cube
+PFE_FLAG_PFD_BSWAP = 0x4    # f64 PFD calls: profs holds byte-reversed 8-byte values
 PFE_PFD_AVGPROF = 2
 PFE_PFD_NSCAL = 8
 PFE_PFD_NDM = 100
@@ -84,9 +85,25 @@ EXPORTED_IO_SYMBOLS = (
     "pfe_phcx_free",
     "pfe_phcx_info_all",
     "pfe_format_rows",
+    "pfe_pfd_scan",
+    "pfe_pfd_count",
+    "pfe_pfd_info_all",
+    "pfe_pfd_fetch",
+    "pfe_pfd_pack",
+    "pfe_pfd_free",
 )
 PFE_PHCX_PROFILE, PFE_PHCX_LYON_DM, PFE_PHCX_SUBBANDS, PFE_PHCX_DM_CURVE, PFE_PHCX_FIT_BLOCK = range(5)
-PFE_IO_STATUS = {0: "ok", 1: "open", 2: "gzip", 3: "xml", 4: "value", 5: "range", 6: "shape"}
+PFE_IO_STATUS = {0: "ok", 1: "open", 2: "gzip", 3: "xml", 4: "value", 5: "range", 6: "shape",
+                 7: "header", 8: "cube"}
+(PFE_PFD_F_DMS, PFE_PFD_F_PERIODS, PFE_PFD_F_PDOTS, PFE_PFD_F_STATS, PFE_PFD_F_SUBFREQS,
+ PFE_PFD_F_HEAD, PFE_PFD_F_FILENM, PFE_PFD_F_CANDNM, PFE_PFD_F_TELESCOPE, PFE_PFD_F_PGDEV,
+ PFE_PFD_F_RASTR, PFE_PFD_F_DECSTR) = range(12)
+PFE_PFD_NHEAD = 23
+# the doubles of PFE_PFD_F_HEAD, in order (PFDData attribute names; orb is seven of them)
+PFD_HEAD_NAMES = ("dt", "startT", "endT", "tepoch", "bepoch", "avgvoverc", "lofreq", "chan_wid",
+                  "bestdm", "topo_p1", "bary_p1", "fold_p1") + ("orb",) * 7 + (
+                      "binspersec", "subdeltafreq", "losubfreq", "varprof")
+assert len(PFD_HEAD_NAMES) == PFE_PFD_NHEAD
 
 
 # handle options (include/pfe.h PFE_OPT_*): name -> (id, default)
@@ -103,7 +120,8 @@ OPTIONS = {
     "lyon8_dm_split": 10,  # 1 (default) chain splits + paired one-chunk rows, 2 splits only, 0 off
     "pfd_global": 11,   # 0 folds that fit stay in LDS (default), 1 every fold through global scratch
     "subf64_global": 12,  # float sub-bands: 0 shapes that fit stay in LDS (default), 1 all in scratch
-    "pfd_f32_chunk": 13,  # float32 folds: folds per pass (0, default: what 1 GiB of part sums holds)
+    # float32 and byte-swapped folds: folds per pass (0, default: what 1 GiB of part sums holds)
+    "pfd_f32_chunk": 13,
 }
 SOLVERS = {"pooled": 0, "batched": 1, "wave": 2}
 
@@ -173,6 +191,16 @@ PHCX_INFO_DTYPE = np.dtype([
     ("ld", "<i8"), ("lfit", "<i8"), ("scal", "<f8", (8,)),
 ])
 assert PHCX_INFO_DTYPE.itemsize == C.sizeof(PhcxInfo)
+
+# numpy view of pfe_pfd_info (include/pfe_io.h), for pfe_pfd_info_all
+PFD_INFO_DTYPE = np.dtype([
+    ("status", "<i4"), ("big_endian", "<i4"), ("npart", "<i4"), ("nsub", "<i4"),
+    ("proflen", "<i4"), ("numdms", "<i4"), ("numperiods", "<i4"), ("numpdots", "<i4"),
+    ("numchan", "<i4"), ("chanpersub", "<i4"), ("has_posn", "<i4"), ("slen", "<i4", (6,)),
+    ("reserved", "<i4"), ("rows", "<i8"), ("stat_rows", "<i8"), ("cube_off", "<i8"),
+    ("stats_off", "<i8"), ("scal", "<f8", (8,)),
+])
+assert PFD_INFO_DTYPE.itemsize == 168
 
 _lib = None
 _lock = threading.Lock()
@@ -254,6 +282,11 @@ def load_library(path: str | None = None) -> C.CDLL:
             "pfe_phcx_pack": (rc, [vp, vp, i64, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp]),
             "pfe_phcx_free": (None, [vp]), "pfe_phcx_info_all": (rc, [vp, vp, i64]),
             "pfe_format_rows": (rc, [vp, vp, vp, i64, i32, i64, i32, vp, i32, vp, i64, ptr(i64)]),
+            "pfe_pfd_scan": (rc, [ptr(C.c_char_p), i64, i32, ptr(vp)]),
+            "pfe_pfd_count": (i64, [vp]), "pfe_pfd_info_all": (rc, [vp, vp, i64]),
+            "pfe_pfd_fetch": (rc, [vp, i64, i32, vp, i64]),
+            "pfe_pfd_pack": (rc, [vp, vp, i64, i32, vp, vp, vp]),
+            "pfe_pfd_free": (None, [vp]),
         }
         assert set(signatures) == set(EXPORTED_SYMBOLS + EXPORTED_IO_SYMBOLS)
         for name, (restype, argtypes) in signatures.items():
@@ -764,11 +797,12 @@ class Engine:
         """The C entry point of a PFD call: its _f32 form for a float32 cube."""
         return getattr(self.lib, "pfe_" + fn + ("_f32" if isinstance(pin, PfdF32In) else ""))
 
-    def pfd_avgprof(self, profs):
+    def pfd_avgprof(self, profs, byteswapped=False):
         """numpy's (profs / proflen).sum() of each fold of a (n,npart,nsub,L) cube, bit for
         bit (pfe_pfd_avgprof; a float32 cube -- numpy array or device tensor -- goes to
         pfe_pfd_avgprof_f32 as it is and gives the value of profs.astype(float64)): the
-        scal[:, 2] every PFD call reads.  Returns (n,) float64 where the cube lives."""
+        scal[:, 2] every PFD call reads.  byteswapped: as in pfd_dmprof.  Returns (n,) float64
+        where the cube lives."""
         if profs.ndim != 4:
             raise ValueError("pfd_avgprof: profs must be (n,npart,nsub,L)")
         n, npart, nsub, L = profs.shape
@@ -785,12 +819,14 @@ class Engine:
             profs = np.ascontiguousarray(profs, dtype=np.float32 if f32 else np.float64)
             out = np.empty((n,), dtype=np.float64)
             flags = 0
+        if byteswapped:
+            flags |= PFE_FLAG_PFD_BSWAP
         fn = self.lib.pfe_pfd_avgprof_f32 if f32 else self.lib.pfe_pfd_avgprof
         self._check(fn(self._h, _ptr(profs), npart, nsub, L, n, _ptr(out), 1, flags))
         return out
 
     def pfd_dmprof(self, profs, subfreqs, scal, profile=True, chis=True, lyon8=True,
-                   derive_avgprof=False):
+                   derive_avgprof=False, byteswapped=False):
         """PFD preprocessing + Lyon features (pfe_pfd_dmprof) for a batch of folds of one
         shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL).
         A float32 cube (numpy array or device tensor) is scored as it is, by the _f32 call of
@@ -799,6 +835,9 @@ class Engine:
         derive_avgprof (this and the other PFD methods): scal[:, 2] is not read; the library
         derives it from the cube on the device (PFE_FLAG_PFD_AVGPROF, the value of
         pfd_avgprof), and scal is left as it is.
+        byteswapped (this and the other PFD methods, f64 cubes only): profs holds 8-byte values
+        whose bytes are reversed, as a big-endian .pfd file holds them (PFE_FLAG_PFD_BSWAP): the
+        bits of the call on profs.byteswap(), the byte order dealt with on the device.
         Returns dict(profile (n,L) f64, chis (n,100) f32, lyon8 (n,8) f64, status (n,))."""
         pin, dev, keep = self._pfd_args(profs, subfreqs, scal, "pfd_dmprof")
         n, L = pin.n, pin.proflen
@@ -815,6 +854,8 @@ class Engine:
             flags = 0
         if derive_avgprof:
             flags |= PFE_FLAG_PFD_AVGPROF
+        if byteswapped:
+            flags |= PFE_FLAG_PFD_BSWAP
         out["profile"] = mk((n, L), f64) if profile else None
         out["chis"] = mk((n, PFE_PFD_NDM), f32) if chis else None
         out["lyon8"] = mk((n, 8), f64) if lyon8 else None
@@ -826,37 +867,44 @@ class Engine:
         del keep
         return out
 
-    def _pfd_scores(self, fn, k, profs, subfreqs, scal, out, status, derive_avgprof=False):
+    def _pfd_scores(self, fn, k, profs, subfreqs, scal, out, status, derive_avgprof=False,
+                    byteswapped=False):
         pin, dev, keep = self._pfd_args(profs, subfreqs, scal, fn)
         out, status, flags = self._outputs(dev, profs, pin.n, k, out, status)
         if derive_avgprof:
             flags |= PFE_FLAG_PFD_AVGPROF
+        if byteswapped:
+            flags |= PFE_FLAG_PFD_BSWAP
         self._check(self._pfd_fn(fn, pin)(self._h, C.byref(pin), _ptr(out), _ptr(status), flags))
         del keep
         return out, status
 
-    def pfd_bates22(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False):
+    def pfd_bates22(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
+                    byteswapped=False):
         """The 22 scores of PFD folds (pfe_pfd_bates22, PFDFile.compute) for a batch of one
         shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL) with
         scal[:, 7] = bary_p1.  Returns (out (n,22) f64, status (n,))."""
         return self._pfd_scores("pfd_bates22", 22, profs, subfreqs, scal, out, status,
-                                derive_avgprof)
+                                derive_avgprof, byteswapped)
 
     # one score group of a batch of folds (PFDOperations; inputs as pfd_bates22)
-    def pfd_params4(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False):
+    def pfd_params4(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
+                    byteswapped=False):
         """getCandidateParameters (pfe_pfd_params4): [period_ms, snr, dm, width], unfiltered."""
         return self._pfd_scores("pfd_params4", 4, profs, subfreqs, scal, out, status,
-                                derive_avgprof)
+                                derive_avgprof, byteswapped)
 
-    def pfd_dmfit4(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False):
+    def pfd_dmfit4(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
+                   byteswapped=False):
         """getDMFittings (pfe_pfd_dmfit4): [s16, s17, Shift (signed), s19]."""
         return self._pfd_scores("pfd_dmfit4", 4, profs, subfreqs, scal, out, status,
-                                derive_avgprof)
+                                derive_avgprof, byteswapped)
 
-    def pfd_subband3(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False):
+    def pfd_subband3(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
+                     byteswapped=False):
         """getSubbandParameters (pfe_pfd_subband3): s20-s22."""
         return self._pfd_scores("pfd_subband3", 3, profs, subfreqs, scal, out, status,
-                                derive_avgprof)
+                                derive_avgprof, byteswapped)
 
 
 class PhcxBatch:
@@ -933,6 +981,108 @@ class PhcxBatch:
             ptr["dmcurve"], ndm or 0, out["scal"].ctypes.data)
         if rc != PFE_OK:
             raise PfeError("pfe_phcx_pack: rows of another shape or failed files")
+        return out
+
+
+class PfdBatch:
+    """.pfd files scanned by the native reader (pfe_pfd_scan): per-file info, the small arrays,
+    and the cubes packed by pread into caller slabs (pfe_pfd_pack)."""
+
+    def __init__(self, paths, threads: int = 0):
+        self.lib = load_library()
+        self.paths = [os.fsencode(p) for p in paths]
+        arr = (C.c_char_p * max(1, len(self.paths)))(*self.paths)
+        h = C.c_void_p()
+        rc = self.lib.pfe_pfd_scan(arr, len(self.paths), int(threads), C.byref(h))
+        if rc != PFE_OK:
+            raise PfeError(f"pfe_pfd_scan failed ({rc})")
+        self._h = h
+
+    def __len__(self):
+        return len(self.paths)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.pfe_pfd_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def infos(self) -> np.ndarray:
+        """Every file's pfe_pfd_info as one structured array (PFD_INFO_DTYPE)."""
+        out = np.empty(len(self.paths), dtype=PFD_INFO_DTYPE)
+        if self.lib.pfe_pfd_info_all(self._h, out.ctypes.data if len(out) else None,
+                                     len(out)) != PFE_OK:
+            raise PfeError("pfe_pfd_info_all failed")
+        return out
+
+    def fetch(self, i: int, field: int, count: int, dtype=np.float64) -> np.ndarray:
+        out = np.empty(count, dtype=dtype)
+        if self.lib.pfe_pfd_fetch(self._h, i, field, out.ctypes.data if count else None,
+                                  count) != PFE_OK:
+            raise PfeError(f"pfe_pfd_fetch({i}, {field}) failed")
+        return out
+
+    def data(self, i: int, info=None):
+        """File i as the PFDData pfd.read(path, avgprof=False) gives: every attribute from the
+        native reader (the cube through pack, a big-endian one byte-swapped here).  For
+        comparing the two readers; the product path packs and never builds one of these."""
+        from .pfd import PFDData
+
+        inf = self.infos()[i] if info is None else info
+        if inf["status"] != 0:
+            raise PfeError(f"file {i}: native reader status {PFE_IO_STATUS.get(int(inf['status']))}")
+        npart, nsub, proflen = int(inf["npart"]), int(inf["nsub"]), int(inf["proflen"])
+        head = self.fetch(i, PFE_PFD_F_HEAD, PFE_PFD_NHEAD)
+        kw = {k: float(v) for k, v in zip(PFD_HEAD_NAMES, head) if k != "orb"}
+        kw["orb"] = tuple(float(v) for v in head[12:19])
+        names = ("filenm", "candnm", "telescope", "pgdev", "rastr", "decstr")
+        for k, name in enumerate(names):
+            kw[name] = self.fetch(i, PFE_PFD_F_FILENM + k, int(inf["slen"][k]), np.uint8).tobytes()
+        a = self.pack([i], (npart, nsub, proflen))
+        profs = a["profs"][0]
+        if inf["big_endian"]:
+            profs = profs.byteswap()
+        return PFDData(
+            swap=">" if inf["big_endian"] else "<", numdms=int(inf["numdms"]),
+            numperiods=int(inf["numperiods"]), numpdots=int(inf["numpdots"]), nsub=nsub,
+            npart=npart, proflen=proflen, numchan=int(inf["numchan"]),
+            chanpersub=int(inf["chanpersub"]),
+            dms=self.fetch(i, PFE_PFD_F_DMS, int(inf["numdms"])),
+            periods=self.fetch(i, PFE_PFD_F_PERIODS, int(inf["numperiods"])),
+            pdots=self.fetch(i, PFE_PFD_F_PDOTS, int(inf["numpdots"])), profs=profs,
+            stats=self.fetch(i, PFE_PFD_F_STATS, npart * nsub * 7).reshape(npart, nsub, 7),
+            subfreqs=self.fetch(i, PFE_PFD_F_SUBFREQS, nsub), avgprof=None, **kw)
+
+    def pack(self, rows, shape, threads: int = 0, alloc=None, cube=True):
+        """Dense inputs of the PFD calls for the given rows (all of one (npart, nsub, proflen)
+        `shape` and one byte order): dict(profs (n,npart,nsub,proflen) float64 holding the
+        files' cube bytes as they are -- byte-reversed values for big-endian files: score with
+        byteswapped=True --, subfreqs (n,nsub), scal (n,8) with scal[:, 2] NaN: score with
+        derive_avgprof=True).  alloc(name, shape, dtype) -> array supplies the destinations
+        (e.g. views of reused pinned slabs); default np.empty.  cube False: no profs."""
+        alloc = alloc or (lambda _k, shp, dt: np.empty(shp, dtype=dt))
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        n = len(rows)
+        npart, nsub, proflen = (int(v) for v in shape)
+        inf = self.infos()[rows]  # the destinations are sized by `shape`: it must be the files'
+        if n and not ((inf["status"] == 0) & (inf["npart"] == npart) & (inf["nsub"] == nsub)
+                      & (inf["proflen"] == proflen)).all():
+            raise PfeError("pfe_pfd_pack: rows of another shape or failed files")
+        out = {"subfreqs": alloc("subfreqs", (n, nsub), np.float64),
+               "scal": alloc("scal", (n, PFE_PFD_NSCAL), np.float64)}
+        if cube:
+            out["profs"] = alloc("profs", (n, npart, nsub, proflen), np.float64)
+        rc = self.lib.pfe_pfd_pack(self._h, rows.ctypes.data, n, int(threads),
+                                   out["profs"].ctypes.data if cube else None,
+                                   out["subfreqs"].ctypes.data, out["scal"].ctypes.data)
+        if rc != PFE_OK:
+            raise PfeError("pfe_pfd_pack: rows of another shape or byte order, failed files, "
+                           "or a file that changed since the scan")
         return out
 
 

@@ -981,7 +981,9 @@ struct PfdF32View {
 };
 // a null or misaligned cube, in the words of the f64 call
 static int pfd_cube_check(pfe_handle* h, const char* fn, const pfe_pfd_in* in, bool f32,
-                          const float* x32) {
+                          const float* x32, uint32_t flags) {
+  if (f32 && (flags & PFE_FLAG_PFD_BSWAP))
+    return set_err(h, PFE_EINVAL, "%s: PFE_FLAG_PFD_BSWAP is for the f64 calls (8-byte values)", fn);
   if ((f32 ? !x32 : !in->profs) || !in->subfreqs || !in->scal)
     return set_err(h, PFE_EINVAL, "%s: null input array", fn);
   if (f32 && ((uintptr_t)x32 & 3))
@@ -990,16 +992,19 @@ static int pfd_cube_check(pfe_handle* h, const char* fn, const pfe_pfd_in* in, b
 }
 // Folds [c0, c0 + cn) of the batch `a`: the whole batch of an f64 call; one pass of a float32
 // call, whose part sums k_pfd_partsum_f32 forms in psum first, for the f64 kernels to read as
-// folds of one part.  Outputs are moved by the caller.
-static int pfd_pass(pfe_handle* h, const char* fn, const pfe::PfdArgs& a, const float* x32,
+// folds of one part; one pass of a PFE_FLAG_PFD_BSWAP call (be: a.profs holds the words),
+// whose part sums k_pfd_partsum_be64 forms.  Outputs are moved by the caller.
+static int pfd_pass(pfe_handle* h, const char* fn, const pfe::PfdArgs& a, const float* x32, bool be,
                     double* psum, int64_t c0, int64_t cn, pfe::PfdArgs& b) {
   b = a;
   b.n = cn;
   b.subfreqs = a.subfreqs + c0 * a.nsub;
   b.scal = a.scal + c0 * PFE_PFD_NSCAL;
-  if (!x32) return PFE_OK;  // c0 = 0, cn = n
-  hipError_t e = pfe::launch_pfd_partsum_f32(x32 + c0 * a.npart * (int64_t)a.nsub * a.L, psum,
-                                             a.npart, a.nsub, a.L, cn, h->stream);
+  if (!x32 && !be) return PFE_OK;  // c0 = 0, cn = n
+  const int64_t at = c0 * a.npart * (int64_t)a.nsub * a.L;
+  hipError_t e =
+      be ? pfe::launch_pfd_partsum_be64(a.profs + at, psum, a.npart, a.nsub, a.L, cn, h->stream)
+         : pfe::launch_pfd_partsum_f32(x32 + at, psum, a.npart, a.nsub, a.L, cn, h->stream);
   if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
   b.profs = psum;
   b.npart = 1;
@@ -1021,14 +1026,17 @@ static int pfd_avg_begin(pfe_handle* h, const pfe_pfd_in* in, double* staged,
   return PFE_OK;
 }
 // the averages of folds [c0, c0 + cn) of the batch `a` into their rows of wscal, from the cube
-// as the call holds it on the device (x32: the floats of an _f32 call)
+// as the call holds it on the device (x32: the floats of an _f32 call; be: the byte-reversed
+// words of a PFE_FLAG_PFD_BSWAP call)
 static int pfd_avg_pass(pfe_handle* h, const char* fn, const pfe::PfdArgs& a, const float* x32,
-                        int64_t c0, int64_t cn, double* csum, double* wscal) {
+                        bool be, int64_t c0, int64_t cn, double* csum, double* wscal) {
   const int64_t E = (int64_t)a.npart * a.nsub * a.L;
   double* out = wscal + c0 * PFE_PFD_NSCAL + PFE_PFD_AVGPROF;
   const hipError_t e =
-      x32 ? pfe::launch_pfd_avgprof_f32(x32 + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL, h->stream)
-          : pfe::launch_pfd_avgprof(a.profs + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL, h->stream);
+      x32  ? pfe::launch_pfd_avgprof_f32(x32 + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL, h->stream)
+      : be ? pfe::launch_pfd_avgprof_be64(a.profs + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL,
+                                          h->stream)
+           : pfe::launch_pfd_avgprof(a.profs + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL, h->stream);
   if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
   return PFE_OK;
 }
@@ -1040,16 +1048,17 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   int64_t n;
   int rc = call_check(h, "pfd_dmprof", in, status != nullptr, n);
   if (rc || n == 0) return rc;
-  if ((rc = pfd_cube_check(h, "pfd_dmprof", in, f32, x32))) return rc;
+  if ((rc = pfd_cube_check(h, "pfd_dmprof", in, f32, x32, flags))) return rc;
   if (in->npart < 1 || in->nsub < 1 || in->proflen < 2)
     return set_err(h, PFE_EINVAL, "pfd_dmprof: shape %dx%dx%d", in->npart, in->nsub, in->proflen);
   const bool useg = pfd_use_global(h, in);
   if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
     return pfd_shape_err(h, "pfd_dmprof", in);
   if ((rc = call_begin(h))) return rc;
-  // folds per pass: all of them, or what the part sums of a float32 cube allow
+  // folds per pass: all of them, or what the part sums of a float32 or byte-reversed cube allow
+  const bool be = flags & PFE_FLAG_PFD_BSWAP, sums = f32 || be;
   const int64_t pass =
-      f32 ? pfe::pfd_f32_chunk(in->nsub, in->proflen, n, h->opt.pfd_f32_chunk) : n;
+      sums ? pfe::pfd_f32_chunk(in->nsub, in->proflen, n, h->opt.pfd_f32_chunk) : n;
   const pfe::PfdGlobalPlan gp = useg ? pfe::pfd_global_plan(in->nsub, in->proflen, pass) : pfe::PfdGlobalPlan();
   hipStream_t st = h->stream;
   pfe::PfdArgs a = pfd_args(h, in);
@@ -1068,8 +1077,8 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   const bool derive = flags & PFE_FLAG_PFD_AVGPROF;
   pfe::PfdDmprofStage s;
   rc = lay_out(h, s, [&](pfe::Arena& A) {
-    return pfe::pfd_dmprof_layout(A, *in, host, profile, chis, lyon8, ws_bytes, f32 ? pass : 0,
-                                  derive);
+    return pfe::pfd_dmprof_layout(A, *in, host, profile, chis, lyon8, ws_bytes, sums ? pass : 0,
+                                  derive, be);
   });
   if (rc || (host && (rc = stage_pfd(h, in, x32, s.in, a)))) return rc;
   double* wscal = nullptr;
@@ -1081,8 +1090,8 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   for (int64_t c0 = 0; c0 < n; c0 += pass) {
     const int64_t cn = n - c0 < pass ? n - c0 : pass;
     pfe::PfdArgs b;
-    if (derive && (rc = pfd_avg_pass(h, "pfd_dmprof", a, x32, c0, cn, s.avg.csum, wscal))) return rc;
-    if ((rc = pfd_pass(h, "pfd_dmprof", a, x32, s.in.psum, c0, cn, b))) return rc;
+    if (derive && (rc = pfd_avg_pass(h, "pfd_dmprof", a, x32, be, c0, cn, s.avg.csum, wscal))) return rc;
+    if ((rc = pfd_pass(h, "pfd_dmprof", a, x32, be, s.in.psum, c0, cn, b))) return rc;
     if (a.profile) b.profile = a.profile + c0 * a.L;
     if (a.chis) b.chis = a.chis + c0 * PFE_PFD_NDM;
     if (a.lyon8) b.lyon8 = a.lyon8 + c0 * 8;
@@ -1120,6 +1129,9 @@ static int pfd_avgprof_call(pfe_handle* h, const double* xd, const float* xf, bo
   if (out_stride < 1) return set_err(h, PFE_EINVAL, "pfd_avgprof: out_stride < 1");
   if (f32 && ((uintptr_t)xf & 3))
     return set_err(h, PFE_EINVAL, "pfd_avgprof: profs not 4-byte aligned");
+  const bool be = flags & PFE_FLAG_PFD_BSWAP;
+  if (f32 && be)
+    return set_err(h, PFE_EINVAL, "pfd_avgprof: PFE_FLAG_PFD_BSWAP is for the f64 call (8-byte values)");
   if (n == 0) return PFE_OK;
   int rc = call_begin(h);
   if (rc) return rc;
@@ -1137,8 +1149,9 @@ static int pfd_avgprof_call(pfe_handle* h, const double* xd, const float* xf, bo
   double* dout = host ? s.out : out;
   const int64_t dstride = host ? 1 : out_stride;
   const hipError_t e =
-      f32 ? pfe::launch_pfd_avgprof_f32(xf, E, proflen, n, s.csum, dout, dstride, h->stream)
-          : pfe::launch_pfd_avgprof(xd, E, proflen, n, s.csum, dout, dstride, h->stream);
+      f32  ? pfe::launch_pfd_avgprof_f32(xf, E, proflen, n, s.csum, dout, dstride, h->stream)
+      : be ? pfe::launch_pfd_avgprof_be64(xd, E, proflen, n, s.csum, dout, dstride, h->stream)
+           : pfe::launch_pfd_avgprof(xd, E, proflen, n, s.csum, dout, dstride, h->stream);
   if (e != hipSuccess)
     return set_err(h, PFE_EDEVICE, "pfd_avgprof launch: %s", hipGetErrorString(e));
   if (host) {
@@ -1190,7 +1203,7 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   int64_t n;
   int rc = call_check(h, fn, in, out && status, n);
   if (rc || n == 0) return rc;
-  if ((rc = pfd_cube_check(h, fn, in, f32, x32))) return rc;
+  if ((rc = pfd_cube_check(h, fn, in, f32, x32, flags))) return rc;
   if (in->npart < 1 || in->nsub < 2 || in->proflen < 8 || in->proflen > 1024)
     return set_err(h, PFE_EINVAL, "%s: shape %dx%dx%d unsupported", fn, in->npart, in->nsub,
                    in->proflen);
@@ -1198,9 +1211,10 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
     return pfd_shape_err(h, fn, in);
   if ((rc = call_begin(h))) return rc;
-  // folds per pass: all of them, or what the part sums of a float32 cube allow
+  // folds per pass: all of them, or what the part sums of a float32 or byte-reversed cube allow
+  const bool be = flags & PFE_FLAG_PFD_BSWAP, sums = f32 || be;
   const int64_t pass =
-      f32 ? pfe::pfd_f32_chunk(in->nsub, in->proflen, n, h->opt.pfd_f32_chunk) : n;
+      sums ? pfe::pfd_f32_chunk(in->nsub, in->proflen, n, h->opt.pfd_f32_chunk) : n;
   auto plan = [&](int64_t cn) {
     return useg ? pfe::pfd_global_plan(in->nsub, in->proflen, cn) : pfe::PfdGlobalPlan();
   };
@@ -1215,7 +1229,7 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   auto walk = [&](int64_t cn) {
     return [&, cn](pfe::Arena& A) {
       return pfe::pfd_scores_layout(A, *in, host, groups, k, plan(cn).bytes(), cus, h->opt,
-                                    f32 ? pass : 0, cn, derive);
+                                    sums ? pass : 0, cn, derive, be);
     };
   };
   if (n % pass) {  // a shorter last pass: its layout fits as well
@@ -1237,8 +1251,8 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
       s = walk(cn)(place);
     }
     pfe::PfdArgs b;
-    if (derive && (rc = pfd_avg_pass(h, fn, a, x32, f0, cn, s.avg.csum, wscal))) return rc;
-    if ((rc = pfd_pass(h, fn, a, x32, s.in.psum, f0, cn, b))) return rc;
+    if (derive && (rc = pfd_avg_pass(h, fn, a, x32, be, f0, cn, s.avg.csum, wscal))) return rc;
+    if ((rc = pfd_pass(h, fn, a, x32, be, s.in.psum, f0, cn, b))) return rc;
     // a group call scores into a 22-column scratch of its own
     double* d22 = all ? dout + f0 * 22 : s.d22;
     if (useg) {

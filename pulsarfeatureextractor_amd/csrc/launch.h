@@ -351,6 +351,22 @@ inline int64_t pfd_f32_chunk(int nsub, int L, int64_t n, int64_t opt) {
 hipError_t launch_pfd_partsum_f32(const float* x, double* s, int npart, int nsub, int L, int64_t n,
                                   hipStream_t st);
 
+// ---- cubes in the opposite byte order: PFE_FLAG_PFD_BSWAP (pfd_be64.hip) ------------------
+// A flagged f64 call is the float32 call with 8-byte words: passes of pfd_f32_chunk folds
+// (PFE_OPT_PFD_F32_CHUNK governs both), k_pfd_partsum_be64 summing the parts of the pass's
+// folds -- every word read through the byte reversal -- into psum, the f64 kernels on psum
+// with npart = 1.  The scratch of a flagged call (be64 = true in the layouts below), in order:
+//   host pointers: [profs: the n x npart x nsub x proflen words as they are][subfreqs][scal]
+//                  [the outputs the call stages][status]
+//   then, host pointers or device:
+//                  [psum: chunk x nsub x proflen doubles]
+//                  [PFE_FLAG_PFD_AVGPROF: avg_csum of chunk folds (and avg_scal, device pointers)]
+//                  [the scratch of the f64 call on the folds of one pass]
+// that is the float32 layout with profs (8 bytes a value) where that has profs32.
+// s[c][e] = v(x[c][0][e]) + ... + v(x[c][npart-1][e]), v the value of the byte-reversed word
+hipError_t launch_pfd_partsum_be64(const double* x, double* s, int npart, int nsub, int L,
+                                   int64_t n, hipStream_t st);
+
 // ---- a fold's average: pfe_pfd_avgprof and PFE_FLAG_PFD_AVGPROF (pfd_avgprof.hip) --------
 // numpy's (profs / proflen).sum() of each fold: k_pfd_avgprof sums every chunk of
 // PFD_AVG_CHUNK values (numpy's reduction buffer) of a fold's E = npart x nsub x proflen into
@@ -362,6 +378,9 @@ hipError_t launch_pfd_avgprof(const double* x, int64_t E, int L, int64_t n, doub
                               double* out, int64_t stride, hipStream_t st);
 hipError_t launch_pfd_avgprof_f32(const float* x, int64_t E, int L, int64_t n, double* csum,
                                   double* out, int64_t stride, hipStream_t st);
+// PFE_FLAG_PFD_BSWAP: x holds byte-reversed doubles, each widened through the reversal
+hipError_t launch_pfd_avgprof_be64(const double* x, int64_t E, int L, int64_t n, double* csum,
+                                   double* out, int64_t stride, hipStream_t st);
 
 // pfe_pfd_avgprof / pfe_pfd_avgprof_f32: a host-pointer call stages the cube (as the values it
 // holds) and its n results; the chunk sums follow
@@ -424,7 +443,9 @@ inline double* pfd_psum_layout(Arena& A, const pfe_pfd_in& in, int64_t f32_chunk
 // pfe_pfd_dmprof: the outputs the caller asked for, then ws_bytes for the two part-sum
 // buffers of the split pipeline or the slabs of the global-memory kernel (PfdGlobalPlan).
 // pfe_pfd_dmprof_f32 (f32_chunk > 0): the same with the float cube and psum; ws_bytes is
-// then what one pass needs.  avgprof (PFE_FLAG_PFD_AVGPROF): pfd_avg_work_layout behind psum
+// then what one pass needs.  avgprof (PFE_FLAG_PFD_AVGPROF): pfd_avg_work_layout behind psum.
+// be64 (PFE_FLAG_PFD_BSWAP, with f32_chunk > 0): the same passes on the cube staged as the
+// 8-byte words it holds (profs)
 struct PfdDmprofStage {
   PfdInputs in;
   PfdAvgWork avg;
@@ -436,11 +457,12 @@ struct PfdDmprofStage {
 };
 inline PfdDmprofStage pfd_dmprof_layout(Arena& A, const pfe_pfd_in& in, bool host, bool profile,
                                         bool chis, bool lyon8, size_t ws_bytes,
-                                        int64_t f32_chunk = 0, bool avgprof = false) {
+                                        int64_t f32_chunk = 0, bool avgprof = false,
+                                        bool be64 = false) {
   PfdDmprofStage s;
   const size_t n = (size_t)in.n;
   if (host) {
-    s.in = pfd_inputs_layout(A, in, f32_chunk > 0);
+    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64);
     if (profile) s.profile = A.take<double>(n * in.proflen, "profile");
     if (chis) s.chis = A.take<float>(n * PFE_PFD_NDM, "chis");
     if (lyon8) s.lyon8 = A.take<double>(n * 8, "lyon8");
@@ -459,7 +481,8 @@ inline PfdDmprofStage pfd_dmprof_layout(Arena& A, const pfe_pfd_in& in, bool hos
 // pass (a pass's chain then works on what the f64 call on that many folds lays out); the
 // staged arrays and psum come first, so they stay put from one pass to the next.  avgprof
 // (PFE_FLAG_PFD_AVGPROF on a call that reads the average): pfd_avg_work_layout behind psum,
-// sized by f32_chunk, so it stays put as well
+// sized by f32_chunk, so it stays put as well.  be64 (PFE_FLAG_PFD_BSWAP, with f32_chunk > 0):
+// the float32 layout with the cube staged as the 8-byte words it holds (profs)
 struct PfdScoresStage {
   PfdInputs in;
   PfdAvgWork avg;
@@ -471,12 +494,13 @@ struct PfdScoresStage {
 inline PfdScoresStage pfd_scores_layout(Arena& A, const pfe_pfd_in& in, bool host,
                                         unsigned groups, int k, size_t g_bytes, int cus,
                                         const Options& o, int64_t f32_chunk = 0,
-                                        int64_t pass = 0, bool avgprof = false) {
+                                        int64_t pass = 0, bool avgprof = false,
+                                        bool be64 = false) {
   PfdScoresStage s;
   const size_t n = (size_t)in.n;
   const int64_t wn = f32_chunk > 0 ? pass : in.n;
   if (host) {
-    s.in = pfd_inputs_layout(A, in, f32_chunk > 0);
+    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64);
     s.out = A.take<double>(n * k, "out");
     s.status = A.take<uint32_t>(n, "status");
   }

@@ -43,6 +43,16 @@ __device__ __forceinline__ int avg_off(uint32_t v) { return (int)(v & 8191u); }
 __device__ __forceinline__ int avg_len(uint32_t v) { return (int)((v >> 13) & 16383u); }
 __device__ __forceinline__ int avg_depth(uint32_t v) { return (int)(v >> 27); }
 
+// an 8-byte value whose bytes are reversed in memory (a big-endian file's double on this
+// machine: PFE_FLAG_PFD_BSWAP): loaded as the word it is, widened to double through the reversal
+struct be64 {
+  unsigned long long w;
+  __device__ __forceinline__ explicit operator double() const {
+    return __builtin_bit_cast(double, __builtin_bswap64(w));
+  }
+};
+static_assert(sizeof(be64) == 8 && alignof(be64) == 8, "a be64 is one word of the cube");
+
 // x / L.  P2 (L a power of two): x * (1 / L), the same real number rounded once, so the same
 // bits (subnormal results included); else the IEEE quotient
 template <bool P2>
@@ -216,6 +226,10 @@ hipError_t launch_pfd_avgprof(const double* x, int64_t E, int L, int64_t n, doub
 hipError_t launch_pfd_avgprof_f32(const float* x, int64_t E, int L, int64_t n, double* csum,
                                   double* out, int64_t stride, hipStream_t st) {
   return launch_avgprof(x, E, L, n, csum, out, stride, st);
+}
+hipError_t launch_pfd_avgprof_be64(const double* x, int64_t E, int L, int64_t n, double* csum,
+                                   double* out, int64_t stride, hipStream_t st) {
+  return launch_avgprof(reinterpret_cast<const be64*>(x), E, L, n, csum, out, stride, st);
 }
 
 }  // namespace pfe

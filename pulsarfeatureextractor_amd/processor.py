@@ -10,8 +10,10 @@ packed into dense arrays and scored in large batches on the GPU through libpfe.
   processPHCXSeparately                                (:91-105, :603-687)
   dmprofPHCX / dmprofSUPERB                            (:255-301, :830-994)
   label                                                (:691-826)
-PFD files (".pfd" in the name, Candidate.py:136) are read by pfd.read and go through
-pfe_pfd_dmprof (dmprof, profile-bin and label modes) and pfe_pfd_bates22 (22 scores).
+PFD files (".pfd" in the name, Candidate.py:136) are scanned by the native .pfd reader, their
+cubes packed by pread into pinned slabs (NativeFolds; pfd.read for the files that reader flags,
+or for all of them with native_pfd=False), and go through pfe_pfd_dmprof (dmprof, profile-bin
+and label modes) and pfe_pfd_bates22 (22 scores).
 
 Streaming: the paths are taken in batches of BATCH files; batch k+1 is parsed on the host
 (native reader threads; the ctypes call releases the GIL) while batch k is scored on the
@@ -263,87 +265,144 @@ def _pfd_call(engine, fn, datas, **kw):
     return getattr(engine, fn)(*_pfd.batch_inputs(datas), **kw)
 
 
+PFD_SLAB_BYTES = 256 << 20  # cube bytes of one pack of natively read folds (at least one fold)
+
+
+class NativeFolds:
+    """Folds of .pfd files the native reader scanned (_native.PfdBatch), in the order of
+    `rows` (file indices of the scan): what score_pfd and its siblings take in place of a list
+    of PFDData.  The files are grouped by (npart, nsub, proflen, byte order); each group is
+    packed -- pfe_pfd_pack: one pread per cube, straight into a reused pinned slab, no value
+    touched on the host -- as many folds at a time as fit `slab_bytes` of cube (at least one:
+    the packs are bounded by bytes, not by a fold count, since one fold may hold 12.6 MB), and
+    each pack is scored by the same Engine.pfd_* methods as parsed folds, with the average
+    derived and a big-endian group's byte order dealt with on the device."""
+
+    def __init__(self, batch, info, rows, slabs, threads=0, slab_bytes=PFD_SLAB_BYTES, run=None):
+        self.batch, self.info, self.rows = batch, info, np.asarray(rows, dtype=np.int64)
+        self.slabs, self.threads, self.slab_bytes, self.run = slabs, threads, int(slab_bytes), run
+
+    def __len__(self):
+        return len(self.rows)
+
+    def _alloc(self, fold_bytes):
+        def alloc(name, shape, dt):
+            if name != "profs":
+                return self.slabs.view("pfd_" + name, shape, dt)
+            # one slab of the fixed size, whatever the pack: never regrown for a larger group
+            flat = self.slabs.view("pfd_profs", (max(self.slab_bytes, fold_bytes),), np.uint8)
+            return flat[:shape[0] * fold_bytes].view(np.float64).reshape(shape)
+        return alloc
+
+    def batches(self, engine):
+        """(positions in this sequence, call) per pack; call(fn, **kw) = engine.<fn> on it."""
+        inf = self.info
+        keys = np.stack([inf[k][self.rows] for k in ("npart", "nsub", "proflen", "big_endian")], 1)
+        for (npart, nsub, proflen, be), pos in _groups(keys, np.arange(len(self.rows))):
+            fold_bytes = 8 * npart * nsub * proflen
+            per = max(1, self.slab_bytes // fold_bytes)
+            for s0 in range(0, len(pos), per):
+                part = pos[s0:s0 + per]
+                t0 = time.perf_counter()
+                a = self.batch.pack(self.rows[part], (npart, nsub, proflen), threads=self.threads,
+                                    alloc=self._alloc(fold_bytes))
+                if self.run is not None:
+                    self.run.add("pack", time.perf_counter() - t0)
+
+                def call(fn, a=a, be=be, **kw):
+                    t1 = time.perf_counter()
+                    try:
+                        return getattr(engine, fn)(a["profs"], a["subfreqs"], a["scal"],
+                                                   derive_avgprof=True, byteswapped=bool(be), **kw)
+                    finally:
+                        if self.run is not None:
+                            self.run.add("gpu", time.perf_counter() - t1)
+
+                yield [int(i) for i in part], call
+
+
+def _fold_batches(datas, engine, batch):
+    """(indices into datas, call) per GPU batch; call(fn, **kw) = engine.<fn> on those folds.
+    datas: parsed folds (PFDData), grouped by shape into batches of `batch`, or NativeFolds."""
+    if isinstance(datas, NativeFolds):
+        yield from datas.batches(engine)
+        return
+    groups: dict = {}
+    for i, d in enumerate(datas):
+        groups.setdefault((d.npart, d.nsub, d.proflen), []).append(i)
+    for _shape, idx in groups.items():
+        for s0 in range(0, len(idx), batch):
+            part = idx[s0:s0 + batch]
+            yield part, (lambda fn, part=part, **kw:
+                         _pfd_call(engine, fn, [datas[i] for i in part], **kw))
+
+
 def score_pfd(datas, engine=None, batch: int = 1 << 14):
-    """PFD preprocessing + Lyon features on the GPU for parsed folds:
+    """PFD preprocessing + Lyon features on the GPU for parsed folds (or NativeFolds):
     returns (lyon8 (n,8), profiles [n arrays], errors [n])."""
     engine = engine or get_engine()
     n = len(datas)
     out = np.full((n, 8), np.nan)
     profiles = [None] * n
     err = [None] * n
-    groups: dict = {}
-    for i, d in enumerate(datas):
-        groups.setdefault((d.npart, d.nsub, d.proflen), []).append(i)
-    for _shape, idx in groups.items():
-        for s0 in range(0, len(idx), batch):
-            part = idx[s0:s0 + batch]
-            try:
-                r = _pfd_call(engine, "pfd_dmprof", [datas[i] for i in part], chis=False)
-            except PfeError as e:  # a shape the library refuses fails its folds, not the run
-                for i in part:
-                    err[i] = f"Exception: {e}"
-                continue
-            for j, i in enumerate(part):
-                profiles[i] = r["profile"][j]
-                if int(r["status"][j]) & 0x20:
-                    err[i] = "Exception: DM curve stat score extraction exception"
-                else:
-                    out[i] = r["lyon8"][j]
+    for part, call in _fold_batches(datas, engine, batch):
+        try:
+            r = call("pfd_dmprof", chis=False)
+        except PfeError as e:  # a shape the library refuses fails its folds, not the run
+            for i in part:
+                err[i] = f"Exception: {e}"
+            continue
+        for j, i in enumerate(part):
+            profiles[i] = r["profile"][j]
+            if int(r["status"][j]) & 0x20:
+                err[i] = "Exception: DM curve stat score extraction exception"
+            else:
+                out[i] = r["lyon8"][j]
     return out, profiles, err
 
 
 def score_pfd22(datas, engine=None, batch: int = 1 << 16):
-    """22 scores of parsed PFD folds on the GPU (pfe_pfd_bates22, PFDFile.compute):
-    returns (scores (n,22), error message or None per fold)."""
+    """22 scores of parsed PFD folds (or NativeFolds) on the GPU (pfe_pfd_bates22,
+    PFDFile.compute): returns (scores (n,22), error message or None per fold)."""
     engine = engine or get_engine()
     n = len(datas)
     out = np.full((n, 22), np.nan)
     err = [None] * n
-    groups: dict = {}
-    for i, d in enumerate(datas):
-        groups.setdefault((d.npart, d.nsub, d.proflen), []).append(i)
-    for _shape, idx in groups.items():
-        for s0 in range(0, len(idx), batch):
-            part = idx[s0:s0 + batch]
-            try:
-                o, st = _pfd_call(engine, "pfd_bates22", [datas[i] for i in part])
-            except PfeError as e:  # a shape the library refuses fails its folds, not the run
-                for i in part:
-                    err[i] = f"Exception: {e}"
-                continue
-            for j, i in enumerate(part):
-                msg = status_error(int(st[j]))
-                if msg:
-                    err[i] = msg
-                else:
-                    out[i] = o[j]
+    for part, call in _fold_batches(datas, engine, batch):
+        try:
+            o, st = call("pfd_bates22")
+        except PfeError as e:  # a shape the library refuses fails its folds, not the run
+            for i in part:
+                err[i] = f"Exception: {e}"
+            continue
+        for j, i in enumerate(part):
+            msg = status_error(int(st[j]))
+            if msg:
+                err[i] = msg
+            else:
+                out[i] = o[j]
     return out, err
 
 
 def pfd_profile_and_curve(datas, engine=None, batch: int = 1 << 14):
-    """The 0..255 profile and the float32 chi^2-vs-DM curve of parsed PFD folds
-    (PFDFile.computeProfileScores :479-492, getDMCurveData :494-520):
+    """The 0..255 profile and the float32 chi^2-vs-DM curve of parsed PFD folds (or
+    NativeFolds) (PFDFile.computeProfileScores :479-492, getDMCurveData :494-520):
     -> (profiles [n arrays], curves [n float32 arrays], error or None per fold)."""
     engine = engine or get_engine()
     n = len(datas)
     profiles, curves, err = [None] * n, [None] * n, [None] * n
-    groups: dict = {}
-    for i, d in enumerate(datas):
-        groups.setdefault((d.npart, d.nsub, d.proflen), []).append(i)
-    for _shape, idx in groups.items():
-        for s0 in range(0, len(idx), batch):
-            part = idx[s0:s0 + batch]
-            try:
-                r = _pfd_call(engine, "pfd_dmprof", [datas[i] for i in part], lyon8=False)
-            except PfeError as e:  # a shape the library refuses fails its folds, not the run
-                for i in part:
-                    err[i] = f"Exception: {e}"
-                continue
-            for j, i in enumerate(part):
-                profiles[i] = r["profile"][j]
-                curves[i] = r["chis"][j]
-                if int(r["status"][j]) & 0x20:
-                    err[i] = "Exception: DM curve extraction exception"
+    for part, call in _fold_batches(datas, engine, batch):
+        try:
+            r = call("pfd_dmprof", lyon8=False)
+        except PfeError as e:  # a shape the library refuses fails its folds, not the run
+            for i in part:
+                err[i] = f"Exception: {e}"
+            continue
+        for j, i in enumerate(part):
+            profiles[i] = r["profile"][j]
+            curves[i] = r["chis"][j]
+            if int(r["status"][j]) & 0x20:
+                err[i] = "Exception: DM curve extraction exception"
     return profiles, curves, err
 
 
@@ -537,14 +596,20 @@ class ParsedBatch:
     """One streamed batch after the host stage.  PHCX / SUPERB files stay inside the native
     reader (`nb`, pfe_phcx_parse) with their infos as one structured array; only the files it
     flags are parsed by the Python parser (`fallback`: {k: (PHCXCandidate | None, error)}, k
-    indexing `px`).  PFD files are read by pfd.read (`rd`)."""
+    indexing `px`).  PFD files are read by pfd.read (`rd`: (PFDData | None, error) per file
+    of `pf`) -- or, native_pfd, scanned by the native reader (`pb`, pfe_pfd_scan, infos
+    `pinfo`), and only the files it flags go through pfd.read: `rd` holds None for a file that
+    stays inside the reader."""
 
-    __slots__ = ("paths", "px", "pf", "nb", "info", "fallback", "rd")
+    __slots__ = ("paths", "px", "pf", "nb", "info", "fallback", "rd", "pb", "pinfo")
 
     def close(self):
         if self.nb is not None:
             self.nb.close()
             self.nb = None
+        if getattr(self, "pb", None) is not None:
+            self.pb.close()
+            self.pb = None
 
 
 class BatchScores:
@@ -701,8 +766,14 @@ class DataProcessor:
 
     def __init__(self, debugFlag=False, engine=None, workers=None, log=print, batch=BATCH,
                  start=0, gpu_batch=1 << 18, metrics_path=None, gpu_depth=2, ramp=True,
-                 gpus=1, devices=None, shard_engine=None, shard_slabs=None):
+                 gpus=1, devices=None, shard_engine=None, shard_slabs=None, native_pfd=True,
+                 pfd_slab_bytes=PFD_SLAB_BYTES):
         self.debug = debugFlag
+        # .pfd files through the native reader (pfe_pfd_scan on the helper thread, pfe_pfd_pack
+        # into the slot's pinned slab, pfd_slab_bytes of cube per pack) when the engine is
+        # libpfe's; False: every file through pfd.read.  The same output bytes either way.
+        self.native_pfd = bool(native_pfd)
+        self.pfd_slab_bytes = int(pfd_slab_bytes)
         # --gpus N: the discovered paths are cut into N contiguous shards, each scored by its
         # own worker process on its own GPU (own reader threads, pinned slabs, engine handles);
         # the parent never touches a GPU and concatenates the shards' outputs in discovery
@@ -819,8 +890,10 @@ class DataProcessor:
     def _parse(self, paths):
         """Host stage (helper thread): PHCX / SUPERB files through the native reader's
         threads (the ctypes call releases the GIL), the Python parser only for files the
-        reader flags; PFD files through pfd.read."""
-        from ._native import PhcxBatch
+        reader flags; PFD files through the native .pfd reader's threads (the scan: header,
+        foldstats, where the cube lies) and pfd.read only for the files that reader flags --
+        or, without native_pfd or under an engine that is not libpfe's, all through pfd.read."""
+        from ._native import Engine, PfdBatch, PhcxBatch
 
         pre = ParsedBatch()
         pre.paths = paths
@@ -832,7 +905,14 @@ class DataProcessor:
             pre.info = pre.nb.infos()
             for k in np.flatnonzero(pre.info["status"] != 0):
                 pre.fallback[int(k)] = _parse_one(paths[pre.px[k]])
-        pre.rd = [_read_pfd(paths[i]) for i in pre.pf]
+        pre.pb, pre.pinfo = None, None
+        if self.native_pfd and pre.pf and (self.engine is None or isinstance(self.engine, Engine)):
+            pre.pb = PfdBatch([paths[i] for i in pre.pf], threads=self.workers)
+            pre.pinfo = pre.pb.infos()
+            pre.rd = [None if st == 0 else _read_pfd(paths[i])
+                      for i, st in zip(pre.pf, pre.pinfo["status"])]
+        else:
+            pre.rd = [_read_pfd(paths[i]) for i in pre.pf]
         return pre
 
     def _eng(self, slot=0):
@@ -960,35 +1040,45 @@ class DataProcessor:
     def _score_pfd(self, pre, mode, res, slot=0):
         pf, rd = pre.pf, pre.rd
         eng = self._eng(slot)
-        good = [k for k, (d, e) in enumerate(rd) if d is not None]
-        for k, (d, e) in enumerate(rd):
-            if d is None:
-                res.err[pf[k]] = e
-        datas = [rd[k][0] for k in good]
-        if not datas:
-            return
+        # files that stay inside the native reader: packed and scored group by group
+        native = [k for k, r in enumerate(rd) if r is None]
+        if native:
+            folds = NativeFolds(pre.pb, pre.pinfo, native, self._slab(slot), self.workers,
+                                self.pfd_slab_bytes, self._run)
+            self._score_folds(folds, [pf[k] for k in native], mode, res, eng)
+        # files read by pfd.read (all of them without native_pfd)
+        good = [k for k, r in enumerate(rd) if r is not None and r[0] is not None]
+        for k, r in enumerate(rd):
+            if r is not None and r[0] is None:
+                res.err[pf[k]] = r[1]
+        if good:
+            self._score_folds([rd[k][0] for k in good], [pf[k] for k in good], mode, res, eng)
+
+    @staticmethod
+    def _score_folds(datas, dest, mode, res, eng):
+        """Folds `datas` (PFDData or NativeFolds) into rows `dest` of the batch's results."""
         if mode == "profile":       # PFDFile.computeProfileScores (:479-492)
             _f, profiles, errs = score_pfd(datas, eng)
-            for j, k in enumerate(good):
+            for j, i in enumerate(dest):
                 if profiles[j] is None:  # the fold's shape was refused
-                    res.err[pf[k]] = errs[j]
+                    res.err[i] = errs[j]
                 else:
-                    res.rows[pf[k]] = np.asarray(profiles[j], dtype=np.float64)
+                    res.rows[i] = np.asarray(profiles[j], dtype=np.float64)
         elif mode == "lyon8":
             feats, _prof, errs = score_pfd(datas, eng)
-            for j, k in enumerate(good):
-                res.mat[pf[k]], res.err[pf[k]] = feats[j], errs[j]
+            for j, i in enumerate(dest):
+                res.mat[i], res.err[i] = feats[j], errs[j]
         else:
             sc, errs = score_pfd22(datas, eng)
             if mode == "label":
                 prof, chis, derr = pfd_profile_and_curve(datas, eng)
-                for j, k in enumerate(good):
-                    res.err[pf[k]] = errs[j] or derr[j]
+                for j, i in enumerate(dest):
+                    res.err[i] = errs[j] or derr[j]
                     if prof[j] is not None:
-                        res.rows[pf[k]] = (sc[j], [float(v) for v in prof[j]], list(chis[j]))
+                        res.rows[i] = (sc[j], [float(v) for v in prof[j]], list(chis[j]))
             else:
-                for j, k in enumerate(good):
-                    res.mat[pf[k]], res.err[pf[k]] = sc[j], errs[j]
+                for j, i in enumerate(dest):
+                    res.mat[i], res.err[i] = sc[j], errs[j]
 
     def _score(self, pre, mode, slot=0):
         """GPU stage on pipeline slot `slot`.  mode: "scores" (22 scores), "profile" (profile
@@ -1227,7 +1317,8 @@ class DataProcessor:
         ctx = mp.get_context("spawn")
         procs, pipes = [], []
         kw = {"debugFlag": self.debug, "workers": threads, "batch": self.batch,
-              "gpu_batch": self.gpu_batch, "gpu_depth": self.depth, "ramp": self.ramp}
+              "gpu_batch": self.gpu_batch, "gpu_depth": self.depth, "ramp": self.ramp,
+              "native_pfd": self.native_pfd, "pfd_slab_bytes": self.pfd_slab_bytes}
         flags = {"phcx": self.phcx, "pfd": self.pfd, "superb": self.superb}
         # the workers start (interpreter, engine, GPU) while the walk is still listing; each
         # gets its shard of paths once the walk is done

@@ -55,7 +55,7 @@ extern "C" {
 /* flags */
 #define PFE_FLAG_DEVICE_PTRS 0x1u /* all array arguments are device pointers */
 /* PFE_FLAG_PFD_AVGPROF 0x2u: the PFD calls only; defined with pfe_pfd_avgprof below */
-/* PFE_FLAG_PFD_BSWAP 0x4u: the f64 PFD calls only; defined with pfe_pfd_avgprof below */
+/* PFE_FLAG_PFD_BSWAP 0x4u: the f64 and _i16 PFD calls only; defined with pfe_pfd_avgprof below */
 
 /* Per-candidate status bits (pfe_bates22).  A non-zero status means the reference would
  * have raised inside Candidate.calculateScores and DataProcessor would have logged the
@@ -544,6 +544,85 @@ int pfe_pfd_avgprof(pfe_handle* h, const double* profs, int32_t npart, int32_t n
                     int32_t proflen, int64_t n, double* out, int64_t out_stride, uint32_t flags);
 int pfe_pfd_avgprof_f32(pfe_handle* h, const float* profs, int32_t npart, int32_t nsub,
                         int32_t proflen, int64_t n, double* out, int64_t out_stride,
+                        uint32_t flags);
+
+/* ---- int16 folds: the five PFD calls on scaled 16-bit values ----------------------------
+ * The most common fold that never was a .pfd file is a fold-mode archive: PSRFITS (dspsr,
+ * PulsarX, every psrchive-based pipeline) keeps a fold as 16-bit integers d with, per
+ * sub-integration x channel, a float32 scale, offset and weight -- a bin's value is d * scl +
+ * offs, a channel of weight 0 is a zapped one -- big-endian, one row of a binary table per
+ * sub-integration.  The _i16 calls score such a fold where it is: the cube is read once, as the
+ * 2-byte values it holds, decoded in registers and never widened in memory, and the inputs may
+ * be the raw rows of an uploaded table, read through two byte strides.
+ *
+ * Contract: every output and the status of an _i16 call is, bit for bit, that of the f64 call
+ * of the same name on the cube
+ *   x[p][s][b] = ((double)d[p][s][b] * (double)scl[p][s] + (double)offs[p][s])   [ * (double)wts[p][s] ]
+ * evaluated in fp64, with the same subfreqs, scal, options and other flags.  The product
+ * (double)d * (double)scl is exact (16 bits times a 24-bit significand, and no float32 exponent
+ * over- or underflows fp64), so the decode rounds once, at + offs (a fused multiply-add gives
+ * the same bits); the multiply by the weight rounds once more, before the value is added to
+ * anything.  wts == NULL: no multiply at all (not a multiply by 1.0).  In
+ * numpy: d.astype(f8) * scl.astype(f8)[..., None] + offs.astype(f8)[..., None], then
+ * * wts.astype(f8)[..., None].  The parts of an element are summed in fp64, S[s][b] = x[0][s][b]
+ * + x[1][s][b] + ... + x[npart-1][s][b], in that order from the value of part 0, and the f64
+ * kernels run on S as folds of one part (the float32 path).  A NaN is a NaN; which payload
+ * survives is unspecified.  Nothing is computed in float32 or in integers, and the inputs are
+ * never written.
+ *
+ * Strides, in bytes.  Both 0: the four arrays are dense, data n x npart x nsub x proflen and
+ * scl, offs, wts n x npart x nsub.  Both non-zero: the four arrays lie in the same rows, one
+ * table row per sub-integration, and share the two strides: value (i,p,s,b) of data is at
+ * (char*)data + i*fold_stride + p*part_stride + 2*(s*proflen + b), value (i,p,s) of scl (offs,
+ * wts) at (char*)scl + i*fold_stride + p*part_stride + 4*s.  For a PSRFITS SUBINT table
+ * part_stride = NAXIS1 and the four pointers are the columns' addresses in row 0.  Required:
+ * part_stride >= 2 x nsub x proflen and a multiple of 4; fold_stride a multiple of 4 and >=
+ * npart x part_stride; data 2-byte aligned; scl, offs and wts 4-byte aligned.  Exactly one
+ * stride non-zero, or any violation, is PFE_EINVAL with a text naming the rule.  Strided input
+ * is for device pointers, where the table's bytes were uploaded as they are: non-zero strides
+ * without PFE_FLAG_DEVICE_PTRS is PFE_EINVAL.  A host-pointer call takes dense arrays and stages
+ * the cube as int16 (a quarter of the f64 call's bytes over the bus) and the parameters as
+ * floats.  8-byte loads (four values) when nsub x proflen is a multiple of 4 and data is 8-byte
+ * aligned at every part, 2-byte loads otherwise; same bits.
+ *
+ * PFE_FLAG_PFD_BSWAP on an _i16 call: data holds 2-byte values and scl, offs, wts 4-byte values
+ * with their bytes reversed (the table as the file holds it); subfreqs, scal and every output
+ * stay native.  Each value is reversed in registers where it is loaded; no swapped copy is made.
+ *
+ * pfe_pfd_avgprof_i16 (it reads the four arrays, the strides and the shape only) and
+ * PFE_FLAG_PFD_AVGPROF on an _i16 call, pass by pass: numpy's (x / proflen).sum() of the decoded
+ * cube x in memory order (p, s, b), by the rule of pfe_pfd_avgprof.
+ *
+ * Everything else -- shape limits, status bits, stream behaviour, the routing options -- is that
+ * of the f64 call of the same name; PFE_EINVAL texts go under the _i16 name.
+ * Scratch: passes of `chunk` folds by the rule of the float32 calls (PFE_OPT_PFD_F32_CHUNK
+ * governs this path too): the arrays a host-pointer call stages (data as int16, then scl, offs
+ * and, when given, wts as floats, then subfreqs, scal and the outputs), then chunk x nsub x
+ * proflen doubles of part sums, then the scratch of the f64 call on `chunk` folds. */
+typedef struct pfe_pfd_i16_in {
+  const int16_t* data;    /* value (i,p,s,b) at (char*)data + i*fold_stride + p*part_stride + 2*(s*proflen + b) */
+  const float* scl;       /* (i,p,s) at (char*)scl + i*fold_stride + p*part_stride + 4*s */
+  const float* offs;      /* as scl */
+  const float* wts;       /* as scl; NULL: no weights, no multiply */
+  int64_t fold_stride;    /* bytes; 0 with part_stride 0 = every array dense */
+  int64_t part_stride;    /* bytes */
+  const double* subfreqs; /* n x nsub */
+  const double* scal;     /* n x PFE_PFD_NSCAL */
+  int32_t npart, nsub, proflen;
+  int64_t n;
+} pfe_pfd_i16_in;
+
+int pfe_pfd_dmprof_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* profile, float* chis,
+                       double* lyon8, uint32_t* status, uint32_t flags);
+int pfe_pfd_bates22_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, uint32_t* status,
+                        uint32_t flags);
+int pfe_pfd_params4_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, uint32_t* status,
+                        uint32_t flags);
+int pfe_pfd_dmfit4_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, uint32_t* status,
+                       uint32_t flags);
+int pfe_pfd_subband3_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, uint32_t* status,
+                         uint32_t flags);
+int pfe_pfd_avgprof_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, int64_t out_stride,
                         uint32_t flags);
 
 /* ---- float32 candidates: the float-array calls on arrays of floats ----------------------

@@ -68,9 +68,15 @@ EXPORTED_SYMBOLS = (
     "pfe_bates22_f32",
     "pfe_pfd_avgprof",
     "pfe_pfd_avgprof_f32",
+    "pfe_pfd_dmprof_i16",
+    "pfe_pfd_bates22_i16",
+    "pfe_pfd_params4_i16",
+    "pfe_pfd_dmfit4_i16",
+    "pfe_pfd_subband3_i16",
+    "pfe_pfd_avgprof_i16",
 )
 PFE_FLAG_PFD_AVGPROF = 0x2  # PFD calls: derive scal[:, PFE_PFD_AVGPROF] from the cube
-PFE_FLAG_PFD_BSWAP = 0x4    # f64 PFD calls: profs holds byte-reversed 8-byte values
+PFE_FLAG_PFD_BSWAP = 0x4    # f64 and int16 PFD calls: the cube (int16: and scl, offs, wts) byte-reversed
 PFE_PFD_AVGPROF = 2
 PFE_PFD_NSCAL = 8
 PFE_PFD_NDM = 100
@@ -168,6 +174,25 @@ class PfdF32In(PfdIn):
     """pfe_pfd_f32_in: the fields of pfe_pfd_in, profs pointing at floats."""
 
 
+class PfdI16In(C.Structure):
+    """pfe_pfd_i16_in: an int16 cube with its float32 scale, offset and weight per (fold, part,
+    sub-band), dense (both strides 0) or in the rows of a table (byte strides)."""
+    _fields_ = [
+        ("data", C.c_void_p),
+        ("scl", C.c_void_p),
+        ("offs", C.c_void_p),
+        ("wts", C.c_void_p),
+        ("fold_stride", C.c_int64),
+        ("part_stride", C.c_int64),
+        ("subfreqs", C.c_void_p),
+        ("scal", C.c_void_p),
+        ("npart", C.c_int32),
+        ("nsub", C.c_int32),
+        ("proflen", C.c_int32),
+        ("n", C.c_int64),
+    ]
+
+
 class PhcxInfo(C.Structure):
     _fields_ = [
         ("status", C.c_int32),
@@ -248,6 +273,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         bates = [vp, ptr(BatesIn), vp, vp, u32]
         pfd = [vp, ptr(PfdIn), vp, vp, u32]
         pfd_f32 = [vp, ptr(PfdF32In), vp, vp, u32]
+        pfd_i16 = [vp, ptr(PfdI16In), vp, vp, u32]
         f64 = [vp, vp, i32, i64, vp, vp, u32]
         bates_f64 = [vp, ptr(BatesF64In), vp, vp, u32]
         bates_f32 = [vp, ptr(BatesF32In), vp, vp, u32]
@@ -275,6 +301,10 @@ def load_library(path: str | None = None) -> C.CDLL:
             "pfe_sinusoid4_f32": (rc, f64), "pfe_gauss7_f32": (rc, f64),
             "pfe_subband3_f32": (rc, bates_f32), "pfe_bates22_f32": (rc, bates_f32),
             "pfe_pfd_avgprof": (rc, avg), "pfe_pfd_avgprof_f32": (rc, avg),
+            "pfe_pfd_dmprof_i16": (rc, [vp, ptr(PfdI16In), vp, vp, vp, vp, u32]),
+            "pfe_pfd_bates22_i16": (rc, pfd_i16), "pfe_pfd_params4_i16": (rc, pfd_i16),
+            "pfe_pfd_dmfit4_i16": (rc, pfd_i16), "pfe_pfd_subband3_i16": (rc, pfd_i16),
+            "pfe_pfd_avgprof_i16": (rc, [vp, ptr(PfdI16In), vp, i64, u32]),
             "pfe_phcx_parse": (rc, [ptr(C.c_char_p), i64, i32, i32, ptr(vp)]),
             "pfe_phcx_count": (i64, [vp]),
             "pfe_phcx_info_get": (rc, [vp, i64, ptr(PhcxInfo)]),
@@ -769,13 +799,81 @@ class Engine:
         return out, st
 
     # -- PFD -----------------------------------------------------------------------------
-    def _pfd_args(self, profs, subfreqs, scal, fn):
+    @staticmethod
+    def _is_i16(profs) -> bool:
+        if isinstance(profs, np.ndarray):
+            return profs.dtype == np.int16
+        return str(getattr(profs, "dtype", "")) == "torch.int16"
+
+    def _pfd_i16_arrays(self, fn, profs, scl, offs, wts):
+        """The four arrays of an int16 cube for pfe_pfd_i16_in -> (data, scl, offs, wts or None,
+        fold_stride, part_stride): host arrays made dense; device tensors as they are -- all
+        contiguous (strides 0, 0), or strided views of one uploaded table whose inner dimensions
+        are dense and whose byte strides agree."""
+        n, npart, nsub, L = profs.shape
+        if scl is None or offs is None:
+            raise ValueError(f"{fn}: scl and offs are required with an int16 cube")
+        par = [("scl", scl), ("offs", offs)] + ([("wts", wts)] if wts is not None else [])
+        for name, a in par:
+            if tuple(a.shape) != (n, npart, nsub):
+                raise ValueError(f"{fn}: {name} must be (n,npart,nsub) = {(n, npart, nsub)}")
+        if not _is_device(profs):
+            for name, a in [("profs", profs)] + par:
+                if not isinstance(a, np.ndarray) or not a.flags.c_contiguous:
+                    raise ValueError(f"{fn}: {name}: host arrays must be dense numpy arrays "
+                                     "(strided input is for device tensors)")
+                if name != "profs" and a.dtype != np.float32:
+                    raise ValueError(f"{fn}: {name} must be float32")
+            return (profs, scl, offs, wts, 0, 0)
+        import torch
+
+        strides = set()
+        for name, a in [("profs", profs)] + par:
+            dt = torch.int16 if name == "profs" else torch.float32
+            if not isinstance(a, torch.Tensor) or not a.is_cuda:
+                raise TypeError(f"{fn}: {name}: expected a CUDA tensor (all arguments device or all host)")
+            if a.dtype != dt:
+                raise ValueError(f"{fn}: {name} must be {dt}")
+            if a.device.index != self.device:
+                raise ValueError(f"{fn}: {name}: on cuda:{a.device.index}, engine is on cuda:{self.device}")
+            if a.is_contiguous():
+                strides.add((0, 0))
+                continue
+            inner = (a.stride(3) == 1 and a.stride(2) == L) if name == "profs" else a.stride(2) == 1
+            if not inner:
+                raise ValueError(f"{fn}: {name}: the inner dimension{'s' if name == 'profs' else ''} "
+                                 "of a strided view must be dense")
+            strides.add((a.stride(0) * a.element_size(), a.stride(1) * a.element_size()))
+        if len(strides) != 1:
+            raise ValueError(f"{fn}: profs, scl, offs and wts must all be contiguous or share one "
+                             f"fold stride and one part stride in bytes, got {sorted(strides)}")
+        fs, ps = strides.pop()
+        return (profs, scl, offs, wts, fs, ps)
+
+    def _pfd_args(self, profs, subfreqs, scal, fn, scl=None, offs=None, wts=None):
         if profs.ndim != 4:
             raise ValueError(f"{fn}: profs must be (n,npart,nsub,L)")
         n, npart, nsub, L = profs.shape
         if tuple(subfreqs.shape) != (n, nsub) or tuple(scal.shape) != (n, PFE_PFD_NSCAL):
             raise ValueError(f"{fn}: subfreqs must be (n,nsub), scal (n,{PFE_PFD_NSCAL})")
         dev = _is_device(profs)
+        if self._is_i16(profs):
+            arrs = self._pfd_i16_arrays(fn, profs, scl, offs, wts)
+            if dev:
+                import torch
+
+                self._dev(subfreqs, "subfreqs", (torch.float64,))
+                self._dev(scal, "scal", (torch.float64,))
+                self._follow_torch()
+            else:
+                subfreqs = np.ascontiguousarray(subfreqs, dtype=np.float64)
+                scal = np.ascontiguousarray(scal, dtype=np.float64)
+            pin = PfdI16In(_ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]),
+                           _ptr(arrs[3]) if arrs[3] is not None else None, arrs[4], arrs[5],
+                           _ptr(subfreqs), _ptr(scal), npart, nsub, L, n)
+            return pin, dev, (arrs, subfreqs, scal)
+        if scl is not None or offs is not None or wts is not None:
+            raise ValueError(f"{fn}: scl, offs and wts go with an int16 cube, profs is {profs.dtype}")
         if dev:
             import torch
 
@@ -794,18 +892,41 @@ class Engine:
         return pin, dev, (profs, subfreqs, scal)
 
     def _pfd_fn(self, fn, pin):
-        """The C entry point of a PFD call: its _f32 form for a float32 cube."""
-        return getattr(self.lib, "pfe_" + fn + ("_f32" if isinstance(pin, PfdF32In) else ""))
+        """The C entry point of a PFD call: its _f32 form for a float32 cube, its _i16 form for
+        an int16 one."""
+        sfx = "_f32" if isinstance(pin, PfdF32In) else "_i16" if isinstance(pin, PfdI16In) else ""
+        return getattr(self.lib, "pfe_" + fn + sfx)
 
-    def pfd_avgprof(self, profs, byteswapped=False):
+    def pfd_avgprof(self, profs, byteswapped=False, scl=None, offs=None, wts=None):
         """numpy's (profs / proflen).sum() of each fold of a (n,npart,nsub,L) cube, bit for
         bit (pfe_pfd_avgprof; a float32 cube -- numpy array or device tensor -- goes to
         pfe_pfd_avgprof_f32 as it is and gives the value of profs.astype(float64)): the
-        scal[:, 2] every PFD call reads.  byteswapped: as in pfd_dmprof.  Returns (n,) float64
-        where the cube lives."""
+        scal[:, 2] every PFD call reads.  byteswapped: as in pfd_dmprof.  An int16 cube with scl,
+        offs (and wts) as in pfd_dmprof goes to pfe_pfd_avgprof_i16 and gives the value of the
+        decoded cube.  Returns (n,) float64 where the cube lives."""
         if profs.ndim != 4:
             raise ValueError("pfd_avgprof: profs must be (n,npart,nsub,L)")
         n, npart, nsub, L = profs.shape
+        if self._is_i16(profs):
+            arrs = self._pfd_i16_arrays("pfd_avgprof", profs, scl, offs, wts)
+            if _is_device(profs):
+                import torch
+
+                self._follow_torch()
+                out = torch.empty((n,), dtype=torch.float64, device=profs.device)
+                flags = PFE_FLAG_DEVICE_PTRS
+            else:
+                out = np.empty((n,), dtype=np.float64)
+                flags = 0
+            if byteswapped:
+                flags |= PFE_FLAG_PFD_BSWAP
+            pin = PfdI16In(_ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]),
+                           _ptr(arrs[3]) if arrs[3] is not None else None, arrs[4], arrs[5],
+                           None, None, npart, nsub, L, n)
+            self._check(self.lib.pfe_pfd_avgprof_i16(self._h, C.byref(pin), _ptr(out), 1, flags))
+            return out
+        if scl is not None or offs is not None or wts is not None:
+            raise ValueError(f"pfd_avgprof: scl, offs and wts go with an int16 cube, profs is {profs.dtype}")
         if _is_device(profs):
             import torch
 
@@ -826,7 +947,7 @@ class Engine:
         return out
 
     def pfd_dmprof(self, profs, subfreqs, scal, profile=True, chis=True, lyon8=True,
-                   derive_avgprof=False, byteswapped=False):
+                   derive_avgprof=False, byteswapped=False, scl=None, offs=None, wts=None):
         """PFD preprocessing + Lyon features (pfe_pfd_dmprof) for a batch of folds of one
         shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL).
         A float32 cube (numpy array or device tensor) is scored as it is, by the _f32 call of
@@ -838,8 +959,16 @@ class Engine:
         byteswapped (this and the other PFD methods, f64 cubes only): profs holds 8-byte values
         whose bytes are reversed, as a big-endian .pfd file holds them (PFE_FLAG_PFD_BSWAP): the
         bits of the call on profs.byteswap(), the byte order dealt with on the device.
+        scl, offs, wts (this and the other PFD methods): an int16 cube -- a fold-mode archive's
+        values -- is scored as it is, by the _i16 call: scl and offs, float32 (n,npart,nsub), are
+        then required, wts (the same) is optional, and the result is the bits of the f64 call on
+        (profs * scl[..., None] + offs[..., None]) [* wts[..., None]] evaluated in float64.
+        Device tensors may be strided views of one uploaded table (inner dimensions dense, one
+        fold and one part stride in bytes shared by all); byteswapped then says that the int16
+        and the float32 values are all byte-reversed.  Giving them with any other cube is a
+        ValueError.
         Returns dict(profile (n,L) f64, chis (n,100) f32, lyon8 (n,8) f64, status (n,))."""
-        pin, dev, keep = self._pfd_args(profs, subfreqs, scal, "pfd_dmprof")
+        pin, dev, keep = self._pfd_args(profs, subfreqs, scal, "pfd_dmprof", scl, offs, wts)
         n, L = pin.n, pin.proflen
         out = {}
         if dev:
@@ -868,8 +997,8 @@ class Engine:
         return out
 
     def _pfd_scores(self, fn, k, profs, subfreqs, scal, out, status, derive_avgprof=False,
-                    byteswapped=False):
-        pin, dev, keep = self._pfd_args(profs, subfreqs, scal, fn)
+                    byteswapped=False, scl=None, offs=None, wts=None):
+        pin, dev, keep = self._pfd_args(profs, subfreqs, scal, fn, scl, offs, wts)
         out, status, flags = self._outputs(dev, profs, pin.n, k, out, status)
         if derive_avgprof:
             flags |= PFE_FLAG_PFD_AVGPROF
@@ -880,31 +1009,31 @@ class Engine:
         return out, status
 
     def pfd_bates22(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
-                    byteswapped=False):
+                    byteswapped=False, scl=None, offs=None, wts=None):
         """The 22 scores of PFD folds (pfe_pfd_bates22, PFDFile.compute) for a batch of one
         shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL) with
         scal[:, 7] = bary_p1.  Returns (out (n,22) f64, status (n,))."""
         return self._pfd_scores("pfd_bates22", 22, profs, subfreqs, scal, out, status,
-                                derive_avgprof, byteswapped)
+                                derive_avgprof, byteswapped, scl, offs, wts)
 
     # one score group of a batch of folds (PFDOperations; inputs as pfd_bates22)
     def pfd_params4(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
-                    byteswapped=False):
+                    byteswapped=False, scl=None, offs=None, wts=None):
         """getCandidateParameters (pfe_pfd_params4): [period_ms, snr, dm, width], unfiltered."""
         return self._pfd_scores("pfd_params4", 4, profs, subfreqs, scal, out, status,
-                                derive_avgprof, byteswapped)
+                                derive_avgprof, byteswapped, scl, offs, wts)
 
     def pfd_dmfit4(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
-                   byteswapped=False):
+                   byteswapped=False, scl=None, offs=None, wts=None):
         """getDMFittings (pfe_pfd_dmfit4): [s16, s17, Shift (signed), s19]."""
         return self._pfd_scores("pfd_dmfit4", 4, profs, subfreqs, scal, out, status,
-                                derive_avgprof, byteswapped)
+                                derive_avgprof, byteswapped, scl, offs, wts)
 
     def pfd_subband3(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
-                     byteswapped=False):
+                     byteswapped=False, scl=None, offs=None, wts=None):
         """getSubbandParameters (pfe_pfd_subband3): s20-s22."""
         return self._pfd_scores("pfd_subband3", 3, profs, subfreqs, scal, out, status,
-                                derive_avgprof, byteswapped)
+                                derive_avgprof, byteswapped, scl, offs, wts)
 
 
 class PhcxBatch:

@@ -943,18 +943,31 @@ static pfe::PfdArgs pfd_args(const pfe_handle* h, const pfe_pfd_in* in) {
   return a;
 }
 // host path: the three inputs into their regions `d`, and `a` reads them there (x32: the
-// float cube of an _f32 call, copied as the floats it is; each pass points a.profs at its sums)
-static int stage_pfd(pfe_handle* h, const pfe_pfd_in* in, const float*& x32,
+// float cube of an _f32 call, copied as the floats it is; q: the dense int16 cube of an _i16
+// call and its parameters, copied as they are; each pass points a.profs at its sums)
+static int stage_pfd(pfe_handle* h, const pfe_pfd_in* in, const float*& x32, pfe::PfdI16Src* q,
                      const pfe::PfdInputs& d, pfe::PfdArgs& a) {
   const size_t n = (size_t)in->n, cube = n * in->npart * in->nsub * in->proflen;
+  const size_t par = n * in->npart * in->nsub;
   int rc;
-  if ((rc = x32 ? stage_in(h, d.profs32, x32, cube) : stage_in(h, d.profs, in->profs, cube)) ||
-      (rc = stage_in(h, d.subfreqs, in->subfreqs, n * in->nsub)) ||
+  if (q) {
+    if ((rc = stage_in(h, d.data16, q->data, cube)) || (rc = stage_in(h, d.scl16, q->scl, par)) ||
+        (rc = stage_in(h, d.offs16, q->offs, par)) ||
+        (q->wts && (rc = stage_in(h, d.wts16, q->wts, par))))
+      return rc;
+    q->data = reinterpret_cast<const char*>(d.data16);
+    q->scl = reinterpret_cast<const char*>(d.scl16);
+    q->offs = reinterpret_cast<const char*>(d.offs16);
+    if (q->wts) q->wts = reinterpret_cast<const char*>(d.wts16);
+  } else if ((rc = x32 ? stage_in(h, d.profs32, x32, cube) : stage_in(h, d.profs, in->profs, cube))) {
+    return rc;
+  }
+  if ((rc = stage_in(h, d.subfreqs, in->subfreqs, n * in->nsub)) ||
       (rc = stage_in(h, d.scal, in->scal, n * PFE_PFD_NSCAL)))
     return rc;
   if (x32)
     x32 = d.profs32;
-  else
+  else if (!q)
     a.profs = d.profs;
   a.subfreqs = d.subfreqs;
   a.scal = d.scal;
@@ -979,6 +992,56 @@ struct PfdF32View {
     view = &in;
   }
 };
+// The pfe_pfd_*_i16 calls go through the bodies of the f64 calls as well: `in` without its
+// cube, the four arrays and their strides beside it (q: null as the caller's `in` was)
+struct PfdI16View {
+  pfe_pfd_in in{};
+  pfe::PfdI16Src src;
+  const pfe_pfd_in* view = nullptr;
+  pfe::PfdI16Src* q = nullptr;
+  PfdI16View(const pfe_pfd_i16_in* f, uint32_t flags) {
+    if (!f) return;
+    in.subfreqs = f->subfreqs;
+    in.scal = f->scal;
+    in.npart = f->npart;
+    in.nsub = f->nsub;
+    in.proflen = f->proflen;
+    in.n = f->n;
+    src = pfe::pfd_i16_src(*f, flags & PFE_FLAG_PFD_BSWAP);
+    view = &in;
+    q = &src;
+  }
+};
+// the four arrays and the strides of an _i16 call, each rule of include/pfe.h by its name
+// (the shape is positive: the caller's shape check has run)
+static int pfd_i16_check(pfe_handle* h, const char* fn, const pfe_pfd_i16_in* f, uint32_t flags,
+                         bool arrays) {
+  if (!f->data || !f->scl || !f->offs || (arrays && (!f->subfreqs || !f->scal)))
+    return set_err(h, PFE_EINVAL, "%s: null input array", fn);
+  if ((uintptr_t)f->data & 1) return set_err(h, PFE_EINVAL, "%s: data not 2-byte aligned", fn);
+  if (((uintptr_t)f->scl | (uintptr_t)f->offs | (uintptr_t)f->wts) & 3)
+    return set_err(h, PFE_EINVAL, "%s: scl, offs and wts must be 4-byte aligned", fn);
+  const int64_t fs = f->fold_stride, ps = f->part_stride;
+  if (!fs && !ps) return PFE_OK;
+  if (!fs || !ps)
+    return set_err(h, PFE_EINVAL,
+                   "%s: fold_stride %lld and part_stride %lld: both 0 (dense arrays) or both non-zero",
+                   fn, (long long)fs, (long long)ps);
+  if (!(flags & PFE_FLAG_DEVICE_PTRS))
+    return set_err(h, PFE_EINVAL,
+                   "%s: strided input is for device pointers (PFE_FLAG_DEVICE_PTRS); a host-pointer "
+                   "call takes dense arrays (both strides 0)", fn);
+  const int64_t row = (int64_t)2 * f->nsub * f->proflen;
+  if (ps < row || ps % 4)
+    return set_err(h, PFE_EINVAL,
+                   "%s: part_stride %lld must be >= 2 x nsub x proflen = %lld and a multiple of 4", fn,
+                   (long long)ps, (long long)row);
+  if (fs % 4 || fs / ps < f->npart)
+    return set_err(h, PFE_EINVAL,
+                   "%s: fold_stride %lld must be >= npart x part_stride = %d x %lld and a multiple of 4",
+                   fn, (long long)fs, f->npart, (long long)ps);
+  return PFE_OK;
+}
 // a null or misaligned cube, in the words of the f64 call
 static int pfd_cube_check(pfe_handle* h, const char* fn, const pfe_pfd_in* in, bool f32,
                           const float* x32, uint32_t flags) {
@@ -993,18 +1056,20 @@ static int pfd_cube_check(pfe_handle* h, const char* fn, const pfe_pfd_in* in, b
 // Folds [c0, c0 + cn) of the batch `a`: the whole batch of an f64 call; one pass of a float32
 // call, whose part sums k_pfd_partsum_f32 forms in psum first, for the f64 kernels to read as
 // folds of one part; one pass of a PFE_FLAG_PFD_BSWAP call (be: a.profs holds the words),
-// whose part sums k_pfd_partsum_be64 forms.  Outputs are moved by the caller.
+// whose part sums k_pfd_partsum_be64 forms; one pass of an _i16 call (q: its arrays on the
+// device), whose values k_pfd_partsum_i16 decodes and sums.  Outputs are moved by the caller.
 static int pfd_pass(pfe_handle* h, const char* fn, const pfe::PfdArgs& a, const float* x32, bool be,
-                    double* psum, int64_t c0, int64_t cn, pfe::PfdArgs& b) {
+                    const pfe::PfdI16Src* q, double* psum, int64_t c0, int64_t cn, pfe::PfdArgs& b) {
   b = a;
   b.n = cn;
   b.subfreqs = a.subfreqs + c0 * a.nsub;
   b.scal = a.scal + c0 * PFE_PFD_NSCAL;
-  if (!x32 && !be) return PFE_OK;  // c0 = 0, cn = n
+  if (!x32 && !be && !q) return PFE_OK;  // c0 = 0, cn = n
   const int64_t at = c0 * a.npart * (int64_t)a.nsub * a.L;
   hipError_t e =
-      be ? pfe::launch_pfd_partsum_be64(a.profs + at, psum, a.npart, a.nsub, a.L, cn, h->stream)
-         : pfe::launch_pfd_partsum_f32(x32 + at, psum, a.npart, a.nsub, a.L, cn, h->stream);
+      q    ? pfe::launch_pfd_partsum_i16(q->from(c0), psum, a.npart, a.nsub, a.L, cn, h->stream)
+      : be ? pfe::launch_pfd_partsum_be64(a.profs + at, psum, a.npart, a.nsub, a.L, cn, h->stream)
+           : pfe::launch_pfd_partsum_f32(x32 + at, psum, a.npart, a.nsub, a.L, cn, h->stream);
   if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
   b.profs = psum;
   b.npart = 1;
@@ -1027,13 +1092,16 @@ static int pfd_avg_begin(pfe_handle* h, const pfe_pfd_in* in, double* staged,
 }
 // the averages of folds [c0, c0 + cn) of the batch `a` into their rows of wscal, from the cube
 // as the call holds it on the device (x32: the floats of an _f32 call; be: the byte-reversed
-// words of a PFE_FLAG_PFD_BSWAP call)
+// words of a PFE_FLAG_PFD_BSWAP call; q: the arrays of an _i16 call)
 static int pfd_avg_pass(pfe_handle* h, const char* fn, const pfe::PfdArgs& a, const float* x32,
-                        bool be, int64_t c0, int64_t cn, double* csum, double* wscal) {
+                        bool be, const pfe::PfdI16Src* q, int64_t c0, int64_t cn, double* csum,
+                        double* wscal) {
   const int64_t E = (int64_t)a.npart * a.nsub * a.L;
   double* out = wscal + c0 * PFE_PFD_NSCAL + PFE_PFD_AVGPROF;
   const hipError_t e =
-      x32  ? pfe::launch_pfd_avgprof_f32(x32 + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL, h->stream)
+      q    ? pfe::launch_pfd_avgprof_i16(q->from(c0), a.npart, a.nsub, a.L, cn, csum, out, PFE_PFD_NSCAL,
+                                         h->stream)
+      : x32 ? pfe::launch_pfd_avgprof_f32(x32 + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL, h->stream)
       : be ? pfe::launch_pfd_avgprof_be64(a.profs + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL,
                                           h->stream)
            : pfe::launch_pfd_avgprof(a.profs + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL, h->stream);
@@ -1041,22 +1109,28 @@ static int pfd_avg_pass(pfe_handle* h, const char* fn, const pfe::PfdArgs& a, co
   return PFE_OK;
 }
 
-// pfe_pfd_dmprof, and pfe_pfd_dmprof_f32 (f32: the cube is x32, in->profs is not read)
+// pfe_pfd_dmprof, pfe_pfd_dmprof_f32 (f32: the cube is x32, in->profs is not read) and
+// pfe_pfd_dmprof_i16 (i16: the caller's struct; q: its arrays, in->profs is not read)
 static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const float* x32,
                            double* profile, float* chis, double* lyon8, uint32_t* status,
-                           uint32_t flags) {
+                           uint32_t flags, const pfe_pfd_i16_in* i16 = nullptr,
+                           pfe::PfdI16Src* q = nullptr) {
+  const char* fn = q ? "pfd_dmprof_i16" : "pfd_dmprof";
   int64_t n;
-  int rc = call_check(h, "pfd_dmprof", in, status != nullptr, n);
+  int rc = call_check(h, fn, in, status != nullptr, n);
   if (rc || n == 0) return rc;
-  if ((rc = pfd_cube_check(h, "pfd_dmprof", in, f32, x32, flags))) return rc;
+  if (!q && (rc = pfd_cube_check(h, fn, in, f32, x32, flags))) return rc;
   if (in->npart < 1 || in->nsub < 1 || in->proflen < 2)
-    return set_err(h, PFE_EINVAL, "pfd_dmprof: shape %dx%dx%d", in->npart, in->nsub, in->proflen);
+    return set_err(h, PFE_EINVAL, "%s: shape %dx%dx%d", fn, in->npart, in->nsub, in->proflen);
+  if (q && (rc = pfd_i16_check(h, fn, i16, flags, true))) return rc;
   const bool useg = pfd_use_global(h, in);
   if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
-    return pfd_shape_err(h, "pfd_dmprof", in);
+    return pfd_shape_err(h, fn, in);
   if ((rc = call_begin(h))) return rc;
-  // folds per pass: all of them, or what the part sums of a float32 or byte-reversed cube allow
-  const bool be = flags & PFE_FLAG_PFD_BSWAP, sums = f32 || be;
+  // folds per pass: all of them, or what the part sums of a float32, byte-reversed or int16
+  // cube allow (an int16 call deals with the byte order in its own kernels)
+  const bool be = !q && (flags & PFE_FLAG_PFD_BSWAP), sums = f32 || be || q;
+  const int ki = !q ? pfe::PFD_I16_NONE : q->wts ? pfe::PFD_I16_WEIGHTS : pfe::PFD_I16_PLAIN;
   const int64_t pass =
       sums ? pfe::pfd_f32_chunk(in->nsub, in->proflen, n, h->opt.pfd_f32_chunk) : n;
   const pfe::PfdGlobalPlan gp = useg ? pfe::pfd_global_plan(in->nsub, in->proflen, pass) : pfe::PfdGlobalPlan();
@@ -1078,9 +1152,9 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   pfe::PfdDmprofStage s;
   rc = lay_out(h, s, [&](pfe::Arena& A) {
     return pfe::pfd_dmprof_layout(A, *in, host, profile, chis, lyon8, ws_bytes, sums ? pass : 0,
-                                  derive, be);
+                                  derive, be, ki);
   });
-  if (rc || (host && (rc = stage_pfd(h, in, x32, s.in, a)))) return rc;
+  if (rc || (host && (rc = stage_pfd(h, in, x32, q, s.in, a)))) return rc;
   double* wscal = nullptr;
   if (derive && (rc = pfd_avg_begin(h, in, host ? s.in.scal : nullptr, s.avg, a, wscal))) return rc;
   a.profile = host ? s.profile : profile;
@@ -1090,8 +1164,8 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   for (int64_t c0 = 0; c0 < n; c0 += pass) {
     const int64_t cn = n - c0 < pass ? n - c0 : pass;
     pfe::PfdArgs b;
-    if (derive && (rc = pfd_avg_pass(h, "pfd_dmprof", a, x32, be, c0, cn, s.avg.csum, wscal))) return rc;
-    if ((rc = pfd_pass(h, "pfd_dmprof", a, x32, be, s.in.psum, c0, cn, b))) return rc;
+    if (derive && (rc = pfd_avg_pass(h, fn, a, x32, be, q, c0, cn, s.avg.csum, wscal))) return rc;
+    if ((rc = pfd_pass(h, fn, a, x32, be, q, s.in.psum, c0, cn, b))) return rc;
     if (a.profile) b.profile = a.profile + c0 * a.L;
     if (a.chis) b.chis = a.chis + c0 * PFE_PFD_NDM;
     if (a.lyon8) b.lyon8 = a.lyon8 + c0 * 8;
@@ -1105,7 +1179,7 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
                                                         chunk, h->pev)
                          : pfe::launch_pfd_dmprof(b, st);
     if (e != hipSuccess)
-      return set_err(h, PFE_EDEVICE, "pfd_dmprof launch: %s", hipGetErrorString(e));
+      return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
   }
   if (host) {
     if ((profile && (rc = fetch(h, profile, a.profile, (size_t)n * in->proflen))) ||
@@ -1181,6 +1255,77 @@ int pfe_pfd_avgprof_f32(pfe_handle* h, const float* profs, int32_t npart, int32_
   return pfd_avgprof_call(h, nullptr, profs, true, npart, nsub, proflen, n, out, out_stride, flags);
 }
 
+// pfe_pfd_avgprof_i16: the four arrays, the strides and the shape of `in` only
+static int pfd_avgprof_i16_call(pfe_handle* h, const pfe_pfd_i16_in* in, double* out,
+                                int64_t out_stride, uint32_t flags) {
+  const char* fn = "pfd_avgprof_i16";
+  if (!h) return PFE_EINVAL;
+  h->err.clear();
+  if (!in || !out) return set_err(h, PFE_EINVAL, "%s: null argument", fn);
+  const int64_t n = in->n;
+  if (n < 0) return set_err(h, PFE_EINVAL, "%s: n < 0", fn);
+  if (in->npart < 1 || in->nsub < 1 || in->proflen < 2)
+    return set_err(h, PFE_EINVAL, "%s: shape %dx%dx%d", fn, in->npart, in->nsub, in->proflen);
+  if (out_stride < 1) return set_err(h, PFE_EINVAL, "%s: out_stride < 1", fn);
+  int rc = pfd_i16_check(h, fn, in, flags, false);
+  if (rc || n == 0) return rc;
+  if ((rc = call_begin(h))) return rc;
+  const int64_t ES = (int64_t)in->npart * in->nsub, E = ES * in->proflen;
+  const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
+  pfe::PfdI16Src q = pfe::pfd_i16_src(*in, flags & PFE_FLAG_PFD_BSWAP);
+  pfe::PfdAvgStage s;
+  rc = lay_out(h, s, [&](pfe::Arena& A) {
+    return pfe::pfd_avgprof_layout(A, E, n, host, false,
+                                   in->wts ? pfe::PFD_I16_WEIGHTS : pfe::PFD_I16_PLAIN, ES);
+  });
+  if (rc) return rc;
+  if (host) {
+    if ((rc = stage_in(h, s.data16, in->data, (size_t)n * E)) ||
+        (rc = stage_in(h, s.scl16, in->scl, (size_t)n * ES)) ||
+        (rc = stage_in(h, s.offs16, in->offs, (size_t)n * ES)) ||
+        (in->wts && (rc = stage_in(h, s.wts16, in->wts, (size_t)n * ES))))
+      return rc;
+    q.data = reinterpret_cast<const char*>(s.data16);
+    q.scl = reinterpret_cast<const char*>(s.scl16);
+    q.offs = reinterpret_cast<const char*>(s.offs16);
+    if (in->wts) q.wts = reinterpret_cast<const char*>(s.wts16);
+  }
+  double* dout = host ? s.out : out;
+  const int64_t dstride = host ? 1 : out_stride;
+  const hipError_t e = pfe::launch_pfd_avgprof_i16(q, in->npart, in->nsub, in->proflen, n, s.csum,
+                                                   dout, dstride, h->stream);
+  if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
+  if (host) {
+    // the n values as one block, then to their places among the caller's doubles
+    std::vector<double> dense;
+    double* dst = out;
+    if (out_stride > 1) {
+      dense.resize((size_t)n);
+      dst = dense.data();
+    }
+    if ((rc = fetch(h, dst, dout, (size_t)n))) return rc;
+    PFE_HIP(h, hipStreamSynchronize(h->stream));
+    if (out_stride > 1)
+      for (int64_t i = 0; i < n; ++i) out[i * out_stride] = dense[(size_t)i];
+  }
+  return call_end(h);
+}
+
+int pfe_pfd_avgprof_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, int64_t out_stride,
+                        uint32_t flags) {
+  return pfd_avgprof_i16_call(h, in, out, out_stride, flags);
+}
+
+int pfe_pfd_dmprof_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* profile, float* chis,
+                       double* lyon8, uint32_t* status, uint32_t flags) {
+  if (h && !in) {
+    h->err.clear();
+    return set_err(h, PFE_EINVAL, "pfd_dmprof_i16: null argument");
+  }
+  PfdI16View v(in, flags);
+  return pfd_dmprof_call(h, v.view, false, nullptr, profile, chis, lyon8, status, flags, in, v.q);
+}
+
 int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* chis,
                    double* lyon8, uint32_t* status, uint32_t flags) {
   return pfd_dmprof_call(h, in, false, nullptr, profile, chis, lyon8, status, flags);
@@ -1199,20 +1344,24 @@ int pfe_pfd_dmprof_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* profile,
 // and their float32 forms (f32: the cube is x32, in->profs is not read)
 static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const float* x32,
                            double* out, uint32_t* status, uint32_t flags, const char* fn,
-                           unsigned groups, int c0, int k) {
+                           unsigned groups, int c0, int k, const pfe_pfd_i16_in* i16 = nullptr,
+                           pfe::PfdI16Src* q = nullptr) {
   int64_t n;
   int rc = call_check(h, fn, in, out && status, n);
   if (rc || n == 0) return rc;
-  if ((rc = pfd_cube_check(h, fn, in, f32, x32, flags))) return rc;
+  if (!q && (rc = pfd_cube_check(h, fn, in, f32, x32, flags))) return rc;
   if (in->npart < 1 || in->nsub < 2 || in->proflen < 8 || in->proflen > 1024)
     return set_err(h, PFE_EINVAL, "%s: shape %dx%dx%d unsupported", fn, in->npart, in->nsub,
                    in->proflen);
+  if (q && (rc = pfd_i16_check(h, fn, i16, flags, true))) return rc;
   const bool useg = pfd_use_global(h, in);
   if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
     return pfd_shape_err(h, fn, in);
   if ((rc = call_begin(h))) return rc;
-  // folds per pass: all of them, or what the part sums of a float32 or byte-reversed cube allow
-  const bool be = flags & PFE_FLAG_PFD_BSWAP, sums = f32 || be;
+  // folds per pass: all of them, or what the part sums of a float32, byte-reversed or int16
+  // cube allow
+  const bool be = !q && (flags & PFE_FLAG_PFD_BSWAP), sums = f32 || be || q;
+  const int ki = !q ? pfe::PFD_I16_NONE : q->wts ? pfe::PFD_I16_WEIGHTS : pfe::PFD_I16_PLAIN;
   const int64_t pass =
       sums ? pfe::pfd_f32_chunk(in->nsub, in->proflen, n, h->opt.pfd_f32_chunk) : n;
   auto plan = [&](int64_t cn) {
@@ -1229,7 +1378,7 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   auto walk = [&](int64_t cn) {
     return [&, cn](pfe::Arena& A) {
       return pfe::pfd_scores_layout(A, *in, host, groups, k, plan(cn).bytes(), cus, h->opt,
-                                    sums ? pass : 0, cn, derive, be);
+                                    sums ? pass : 0, cn, derive, be, ki);
     };
   };
   if (n % pass) {  // a shorter last pass: its layout fits as well
@@ -1239,7 +1388,7 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   }
   pfe::PfdScoresStage s;
   rc = lay_out(h, s, walk(pass));
-  if (rc || (host && (rc = stage_pfd(h, in, x32, s.in, a)))) return rc;
+  if (rc || (host && (rc = stage_pfd(h, in, x32, q, s.in, a)))) return rc;
   double* wscal = nullptr;
   if (derive && (rc = pfd_avg_begin(h, in, host ? s.in.scal : nullptr, s.avg, a, wscal))) return rc;
   double* dout = host ? s.out : out;
@@ -1251,8 +1400,8 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
       s = walk(cn)(place);
     }
     pfe::PfdArgs b;
-    if (derive && (rc = pfd_avg_pass(h, fn, a, x32, be, f0, cn, s.avg.csum, wscal))) return rc;
-    if ((rc = pfd_pass(h, fn, a, x32, be, s.in.psum, f0, cn, b))) return rc;
+    if (derive && (rc = pfd_avg_pass(h, fn, a, x32, be, q, f0, cn, s.avg.csum, wscal))) return rc;
+    if ((rc = pfd_pass(h, fn, a, x32, be, q, s.in.psum, f0, cn, b))) return rc;
     // a group call scores into a 22-column scratch of its own
     double* d22 = all ? dout + f0 * 22 : s.d22;
     if (useg) {
@@ -1297,7 +1446,32 @@ static int pfd_scores_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, 
   return pfd_scores_call(h, v.view, true, v.x32, out, status, flags, c.fn, c.groups, c.c0, c.k);
 }
 
+static int pfd_scores_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, uint32_t* status,
+                          uint32_t flags, const PfdScores& c) {
+  PfdI16View v(in, flags);
+  const std::string fn = std::string(c.fn) + "_i16";
+  return pfd_scores_call(h, v.view, false, nullptr, out, status, flags, fn.c_str(), c.groups, c.c0,
+                         c.k, in, v.q);
+}
+
 extern "C" {
+
+int pfe_pfd_bates22_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, uint32_t* status,
+                        uint32_t flags) {
+  return pfd_scores_i16(h, in, out, status, flags, PFD_BATES22);
+}
+int pfe_pfd_params4_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, uint32_t* status,
+                        uint32_t flags) {
+  return pfd_scores_i16(h, in, out, status, flags, PFD_PARAMS4);
+}
+int pfe_pfd_dmfit4_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, uint32_t* status,
+                       uint32_t flags) {
+  return pfd_scores_i16(h, in, out, status, flags, PFD_DMFIT4);
+}
+int pfe_pfd_subband3_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, uint32_t* status,
+                         uint32_t flags) {
+  return pfd_scores_i16(h, in, out, status, flags, PFD_SUBBAND3);
+}
 
 int pfe_pfd_bates22(pfe_handle* h, const pfe_pfd_in* in, double* out, uint32_t* status,
                     uint32_t flags) {

@@ -367,6 +367,59 @@ hipError_t launch_pfd_partsum_f32(const float* x, double* s, int npart, int nsub
 hipError_t launch_pfd_partsum_be64(const double* x, double* s, int npart, int nsub, int L,
                                    int64_t n, hipStream_t st);
 
+// ---- int16 fold cubes: the pfe_pfd_*_i16 calls (pfd_i16.hip) -----------------------------
+// An int16 call is the float32 call with 2-byte values and their float32 scale, offset and
+// weight per (fold, part, sub-band): passes of pfd_f32_chunk folds (PFE_OPT_PFD_F32_CHUNK
+// governs this path too), k_pfd_partsum_i16 decoding and summing the parts of the pass's folds
+// into psum, the f64 kernels on psum with npart = 1.  The scratch of an int16 call (i16 != 0 in
+// the layouts below), in order:
+//   host pointers: [data16: the n x npart x nsub x proflen values][scl16][offs16][wts16, when
+//                  weights are given: n x npart x nsub floats each][subfreqs][scal]
+//                  [the outputs the call stages][status]
+//   then, host pointers or device:
+//                  [psum: chunk x nsub x proflen doubles]
+//                  [PFE_FLAG_PFD_AVGPROF: avg_csum of chunk folds (and avg_scal, device pointers)]
+//                  [the scratch of the f64 call on the folds of one pass]
+enum PfdI16 { PFD_I16_NONE = 0, PFD_I16_PLAIN = 1, PFD_I16_WEIGHTS = 2 };
+// the four arrays of an int16 call as the kernels read them: value (c, p, s, b) of data at
+// data + c*dfs + p*dps + 2*(s*L + b), value (c, p, s) of scl (offs, wts) at scl + c*pfs +
+// p*pps + 4*s.  Dense arrays have the strides of their shapes; table rows share one pair
+struct PfdI16Src {
+  const char *data = nullptr, *scl = nullptr, *offs = nullptr, *wts = nullptr;  // wts may be null
+  int64_t dfs = 0, dps = 0, pfs = 0, pps = 0;  // bytes
+  bool bswap = false;                          // PFE_FLAG_PFD_BSWAP: every value byte-reversed
+  PfdI16Src from(int64_t c0) const {           // folds c0 ..
+    PfdI16Src r = *this;
+    r.data += c0 * dfs;
+    r.scl += c0 * pfs;
+    r.offs += c0 * pfs;
+    if (wts) r.wts += c0 * pfs;
+    return r;
+  }
+};
+inline PfdI16Src pfd_i16_src(const pfe_pfd_i16_in& in, bool bswap) {
+  PfdI16Src q;
+  q.data = reinterpret_cast<const char*>(in.data);
+  q.scl = reinterpret_cast<const char*>(in.scl);
+  q.offs = reinterpret_cast<const char*>(in.offs);
+  q.wts = reinterpret_cast<const char*>(in.wts);
+  if (in.fold_stride) {
+    q.dfs = q.pfs = in.fold_stride;
+    q.dps = q.pps = in.part_stride;
+  } else {
+    q.dps = (int64_t)2 * in.nsub * in.proflen;
+    q.dfs = q.dps * in.npart;
+    q.pps = (int64_t)4 * in.nsub;
+    q.pfs = q.pps * in.npart;
+  }
+  q.bswap = bswap;
+  return q;
+}
+// s[c][e] = x(c,0,e) + ... + x(c,npart-1,e), x the decoded value ((double)d * scl + offs, then
+// * wts when given), e over nsub x L, c over n folds; s dense
+hipError_t launch_pfd_partsum_i16(const PfdI16Src& x, double* s, int npart, int nsub, int L,
+                                  int64_t n, hipStream_t st);
+
 // ---- a fold's average: pfe_pfd_avgprof and PFE_FLAG_PFD_AVGPROF (pfd_avgprof.hip) --------
 // numpy's (profs / proflen).sum() of each fold: k_pfd_avgprof sums every chunk of
 // PFD_AVG_CHUNK values (numpy's reduction buffer) of a fold's E = npart x nsub x proflen into
@@ -381,18 +434,30 @@ hipError_t launch_pfd_avgprof_f32(const float* x, int64_t E, int L, int64_t n, d
 // PFE_FLAG_PFD_BSWAP: x holds byte-reversed doubles, each widened through the reversal
 hipError_t launch_pfd_avgprof_be64(const double* x, int64_t E, int L, int64_t n, double* csum,
                                    double* out, int64_t stride, hipStream_t st);
+// an int16 cube: each value decoded where it is loaded, the n folds' E = npart x nsub x L values
+// in the order (p, s, b)
+hipError_t launch_pfd_avgprof_i16(const PfdI16Src& x, int npart, int nsub, int L, int64_t n,
+                                  double* csum, double* out, int64_t stride, hipStream_t st);
 
 // pfe_pfd_avgprof / pfe_pfd_avgprof_f32: a host-pointer call stages the cube (as the values it
 // holds) and its n results; the chunk sums follow
 struct PfdAvgStage {
   double* profs = nullptr;
   float* profs32 = nullptr;
+  int16_t* data16 = nullptr;  // pfe_pfd_avgprof_i16: the cube and its parameters (ES = npart x nsub)
+  float *scl16 = nullptr, *offs16 = nullptr, *wts16 = nullptr;
   double *out = nullptr, *csum = nullptr;
 };
-inline PfdAvgStage pfd_avgprof_layout(Arena& A, int64_t E, int64_t n, bool host, bool f32) {
+inline PfdAvgStage pfd_avgprof_layout(Arena& A, int64_t E, int64_t n, bool host, bool f32,
+                                      int i16 = PFD_I16_NONE, int64_t ES = 0) {
   PfdAvgStage s;
   if (host) {
-    if (f32)
+    if (i16) {
+      s.data16 = A.take<int16_t>((size_t)n * E, "data16");
+      s.scl16 = A.take<float>((size_t)n * ES, "scl16");
+      s.offs16 = A.take<float>((size_t)n * ES, "offs16");
+      if (i16 == PFD_I16_WEIGHTS) s.wts16 = A.take<float>((size_t)n * ES, "wts16");
+    } else if (f32)
       s.profs32 = A.take<float>((size_t)n * E, "profs32");
     else
       s.profs = A.take<double>((size_t)n * E, "profs");
@@ -423,12 +488,21 @@ inline PfdAvgWork pfd_avg_work_layout(Arena& A, const pfe_pfd_in& in, bool host,
 struct PfdInputs {
   double *profs = nullptr, *subfreqs = nullptr, *scal = nullptr;
   float* profs32 = nullptr;
+  int16_t* data16 = nullptr;  // an int16 call: the cube and its parameters
+  float *scl16 = nullptr, *offs16 = nullptr, *wts16 = nullptr;
   double* psum = nullptr;
 };
-inline PfdInputs pfd_inputs_layout(Arena& A, const pfe_pfd_in& in, bool f32 = false) {
+inline PfdInputs pfd_inputs_layout(Arena& A, const pfe_pfd_in& in, bool f32 = false,
+                                   int i16 = PFD_I16_NONE) {
   PfdInputs s;
   const size_t n = (size_t)in.n, cube = n * in.npart * in.nsub * in.proflen;
-  if (f32)
+  if (i16) {
+    const size_t par = n * in.npart * in.nsub;
+    s.data16 = A.take<int16_t>(cube, "data16");
+    s.scl16 = A.take<float>(par, "scl16");
+    s.offs16 = A.take<float>(par, "offs16");
+    if (i16 == PFD_I16_WEIGHTS) s.wts16 = A.take<float>(par, "wts16");
+  } else if (f32)
     s.profs32 = A.take<float>(cube, "profs32");
   else
     s.profs = A.take<double>(cube, "profs");
@@ -445,7 +519,8 @@ inline double* pfd_psum_layout(Arena& A, const pfe_pfd_in& in, int64_t f32_chunk
 // pfe_pfd_dmprof_f32 (f32_chunk > 0): the same with the float cube and psum; ws_bytes is
 // then what one pass needs.  avgprof (PFE_FLAG_PFD_AVGPROF): pfd_avg_work_layout behind psum.
 // be64 (PFE_FLAG_PFD_BSWAP, with f32_chunk > 0): the same passes on the cube staged as the
-// 8-byte words it holds (profs)
+// 8-byte words it holds (profs).  i16 (an int16 call, with f32_chunk > 0; be64 false, whatever
+// the flag): the same passes on the cube staged as int16 with its parameters
 struct PfdDmprofStage {
   PfdInputs in;
   PfdAvgWork avg;
@@ -458,11 +533,11 @@ struct PfdDmprofStage {
 inline PfdDmprofStage pfd_dmprof_layout(Arena& A, const pfe_pfd_in& in, bool host, bool profile,
                                         bool chis, bool lyon8, size_t ws_bytes,
                                         int64_t f32_chunk = 0, bool avgprof = false,
-                                        bool be64 = false) {
+                                        bool be64 = false, int i16 = PFD_I16_NONE) {
   PfdDmprofStage s;
   const size_t n = (size_t)in.n;
   if (host) {
-    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64);
+    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64, i16);
     if (profile) s.profile = A.take<double>(n * in.proflen, "profile");
     if (chis) s.chis = A.take<float>(n * PFE_PFD_NDM, "chis");
     if (lyon8) s.lyon8 = A.take<double>(n * 8, "lyon8");
@@ -482,7 +557,8 @@ inline PfdDmprofStage pfd_dmprof_layout(Arena& A, const pfe_pfd_in& in, bool hos
 // staged arrays and psum come first, so they stay put from one pass to the next.  avgprof
 // (PFE_FLAG_PFD_AVGPROF on a call that reads the average): pfd_avg_work_layout behind psum,
 // sized by f32_chunk, so it stays put as well.  be64 (PFE_FLAG_PFD_BSWAP, with f32_chunk > 0):
-// the float32 layout with the cube staged as the 8-byte words it holds (profs)
+// the float32 layout with the cube staged as the 8-byte words it holds (profs).  i16 (an int16
+// call, with f32_chunk > 0; be64 false): the float32 layout with the int16 cube and its parameters
 struct PfdScoresStage {
   PfdInputs in;
   PfdAvgWork avg;
@@ -495,12 +571,12 @@ inline PfdScoresStage pfd_scores_layout(Arena& A, const pfe_pfd_in& in, bool hos
                                         unsigned groups, int k, size_t g_bytes, int cus,
                                         const Options& o, int64_t f32_chunk = 0,
                                         int64_t pass = 0, bool avgprof = false,
-                                        bool be64 = false) {
+                                        bool be64 = false, int i16 = PFD_I16_NONE) {
   PfdScoresStage s;
   const size_t n = (size_t)in.n;
   const int64_t wn = f32_chunk > 0 ? pass : in.n;
   if (host) {
-    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64);
+    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64, i16);
     s.out = A.take<double>(n * k, "out");
     s.status = A.take<uint32_t>(n, "status");
   }

@@ -19,6 +19,8 @@
 // the fold's chunk sums in order.  Two plain kernels on one stream; no atomics.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "launch.h"
 #include "np_sum.h"
 
@@ -53,6 +55,77 @@ struct be64 {
 };
 static_assert(sizeof(be64) == 8 && alignof(be64) == 8, "a be64 is one word of the cube");
 
+// A value of an int16 cube (pfd_i16.hip) as loaded with the scale, offset and weight of its
+// (part, sub-band): widened to double through the decode, (double)d * scl + offs rounded once
+// (the product is exact, so the fused multiply-add rounds where multiply-then-add does), then,
+// WT, times the weight rounded once.  BS: every value byte-reversed (PFE_FLAG_PFD_BSWAP)
+template <bool BS, bool WT>
+struct i16_elem {
+  unsigned d, a, o, w;
+  static __device__ __forceinline__ double f32(unsigned v) {
+    return (double)__builtin_bit_cast(float, BS ? __builtin_bswap32(v) : v);
+  }
+  __device__ __forceinline__ explicit operator double() const {
+    const unsigned short h = (unsigned short)d;
+    const double x = __builtin_fma((double)(int)(short)(BS ? __builtin_bswap16(h) : h), f32(a), f32(o));
+    if constexpr (WT) return x * f32(w);
+    return x;
+  }
+};
+// Where a pointer into a float or double cube stands, for one fold of an int16 cube: values
+// [at, ...) of the fold in the order (p, s, b).  at = the chunk's first value as part p0 and
+// element r0 of that part, plus what has been added since (a chunk holds <= 8192 values and a
+// part E1 = nsub x L < 2^31, so the 32-bit division is by a value that fits)
+template <bool BS, bool WT>
+struct i16_cursor {
+  const char *data, *scl, *offs, *wts;  // of the fold's part p0
+  int64_t dps, pps;
+  unsigned E1, L, r;
+  __device__ __forceinline__ i16_cursor operator+(int k) const {
+    i16_cursor c = *this;
+    c.r += (unsigned)k;
+    return c;
+  }
+  __device__ __forceinline__ i16_elem<BS, WT> operator[](int k) const {
+    const unsigned j = r + (unsigned)k, p = j / E1, e = j - p * E1;
+    const int64_t at = (int64_t)p * pps + (int64_t)4 * (e / L);
+    i16_elem<BS, WT> v;
+    v.d = *reinterpret_cast<const unsigned short*>(data + (int64_t)p * dps + (int64_t)2 * e);
+    v.a = *reinterpret_cast<const unsigned*>(scl + at);
+    v.o = *reinterpret_cast<const unsigned*>(offs + at);
+    v.w = WT ? *reinterpret_cast<const unsigned*>(wts + at) : 0u;
+    return v;
+  }
+};
+// the int16 cube of a launch: what a `const T* X` is for the others
+template <bool BS, bool WT>
+struct i16_cube {
+  PfdI16Src x;
+  unsigned E1, L;
+};
+
+// the values of `fold` from its e0-th on: a pointer, or a cursor
+template <typename T>
+__device__ __forceinline__ const T* avg_at(const T* X, int64_t fold, int64_t E, int64_t e0) {
+  return X + fold * E + e0;
+}
+template <bool BS, bool WT>
+__device__ __forceinline__ i16_cursor<BS, WT> avg_at(const i16_cube<BS, WT>& X, int64_t fold, int64_t,
+                                                      int64_t e0) {
+  const int64_t p0 = e0 / X.E1;
+  i16_cursor<BS, WT> c;
+  c.data = X.x.data + fold * X.x.dfs + p0 * X.x.dps;
+  c.scl = X.x.scl + fold * X.x.pfs + p0 * X.x.pps;
+  c.offs = X.x.offs + fold * X.x.pfs + p0 * X.x.pps;
+  c.wts = WT ? X.x.wts + fold * X.x.pfs + p0 * X.x.pps : nullptr;
+  c.dps = X.x.dps;
+  c.pps = X.x.pps;
+  c.E1 = X.E1;
+  c.L = X.L;
+  c.r = (unsigned)(e0 - p0 * X.E1);
+  return c;
+}
+
 // x / L.  P2 (L a power of two): x * (1 / L), the same real number rounded once, so the same
 // bits (subnormal results included); else the IEEE quotient
 template <bool P2>
@@ -64,10 +137,10 @@ __device__ __forceinline__ double avg_scale(double x, double dl, double inv) {
 // numpy's leaf sum of p[0 .. len), 8 <= len <= 128, scaled: the result in every lane of the
 // 8-lane group (t = lane & 7).  Every lane of the wave is here (the DPP steps read within a
 // group), groups may hold leaves of different lengths: selects, no divergent branch.
-template <typename T, bool P2>
-__device__ __forceinline__ double avg_leaf(const T* p, int len, int t, double dl, double inv) {
+template <typename Cur, bool P2>
+__device__ __forceinline__ double avg_leaf(const Cur p, int len, int t, double dl, double inv) {
   const int nb = len & ~7;
-  T raw[16];
+  std::remove_cv_t<std::remove_reference_t<decltype(p[0])>> raw[16];
 #pragma unroll
   for (int m = 0; m < 16; ++m) raw[m] = p[min(t + 8 * m, len - 1)];
   double r = avg_scale<P2>((double)raw[0], dl, inv);
@@ -89,11 +162,11 @@ __device__ __forceinline__ double avg_leaf(const T* p, int len, int t, double dl
 }
 
 // csum[fold * nch + chunk] = numpy's pairwise sum of the chunk's scaled values.  X: n folds of
-// E values, dense; nch = ceil(E / 8192); total = n * nch waves.
-template <typename T, bool P2>
-__global__ __launch_bounds__(AVG_WPB * 64) void k_pfd_avgprof(const T* __restrict__ X, int64_t E,
-                                                             int nch, int64_t total, double dl,
-                                                             double inv,
+// E values, dense (Src a pointer to them), or the int16 cube of pfd_i16.hip (Src an i16_cube);
+// nch = ceil(E / 8192); total = n * nch waves.
+template <typename Src, bool P2>
+__global__ __launch_bounds__(AVG_WPB * 64) void k_pfd_avgprof(const Src X, int64_t E, int nch,
+                                                             int64_t total, double dl, double inv,
                                                              double* __restrict__ csum) {
   __shared__ double s_sum[AVG_WPB][AVG_MAX_LEAVES];
   __shared__ uint32_t s_tab[AVG_WPB][AVG_MAX_LEAVES];
@@ -106,7 +179,7 @@ __global__ __launch_bounds__(AVG_WPB * 64) void k_pfd_avgprof(const T* __restric
   const int ch = (int)(wg - fold * nch);
   const int64_t e0 = (int64_t)ch * PFD_AVG_CHUNK;
   const int n = (int)(E - e0 < PFD_AVG_CHUNK ? E - e0 : PFD_AVG_CHUNK);
-  const T* x = X + fold * E + e0;
+  const auto x = avg_at(X, fold, E, e0);
 
   if (n < 8) {  // 0.0 + y0 + y1 ...
     double r = 0.0;
@@ -153,7 +226,7 @@ __global__ __launch_bounds__(AVG_WPB * 64) void k_pfd_avgprof(const T* __restric
       off = avg_off(v);
       len = avg_len(v);
     }
-    const double s = avg_leaf<T, P2>(x + off, len, t, dl, inv);
+    const double s = avg_leaf<decltype(x + off), P2>(x + off, len, t, dl, inv);
     if (t == 0 && b + g < nleaf) s_sum[w][b + g] = s;
   }
   lds_sync();
@@ -196,8 +269,8 @@ __global__ __launch_bounds__(256) void k_pfd_avgprof_fin(const double* __restric
   out[i * stride] = r;
 }
 
-template <typename T>
-static hipError_t launch_avgprof(const T* x, int64_t E, int L, int64_t n, double* csum, double* out,
+template <typename Src>
+static hipError_t launch_avgprof(const Src x, int64_t E, int L, int64_t n, double* csum, double* out,
                                  int64_t stride, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   const int64_t nch = pfd_avg_chunks(E), total = n * nch;
@@ -207,10 +280,10 @@ static hipError_t launch_avgprof(const T* x, int64_t E, int L, int64_t n, double
   const double dl = (double)L, inv = 1.0 / dl;  // exact for a power of two
   const dim3 grid((unsigned)blocks), block(AVG_WPB * 64);
   if (p2)
-    hipLaunchKernelGGL((k_pfd_avgprof<T, true>), grid, block, 0, st, x, E, (int)nch, total, dl, inv,
+    hipLaunchKernelGGL((k_pfd_avgprof<Src, true>), grid, block, 0, st, x, E, (int)nch, total, dl, inv,
                        csum);
   else
-    hipLaunchKernelGGL((k_pfd_avgprof<T, false>), grid, block, 0, st, x, E, (int)nch, total, dl,
+    hipLaunchKernelGGL((k_pfd_avgprof<Src, false>), grid, block, 0, st, x, E, (int)nch, total, dl,
                        inv, csum);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
@@ -230,6 +303,19 @@ hipError_t launch_pfd_avgprof_f32(const float* x, int64_t E, int L, int64_t n, d
 hipError_t launch_pfd_avgprof_be64(const double* x, int64_t E, int L, int64_t n, double* csum,
                                    double* out, int64_t stride, hipStream_t st) {
   return launch_avgprof(reinterpret_cast<const be64*>(x), E, L, n, csum, out, stride, st);
+}
+template <bool BS>
+static hipError_t launch_avgprof_i16(const PfdI16Src& x, unsigned E1, int64_t E, int L, int64_t n,
+                                     double* csum, double* out, int64_t stride, hipStream_t st) {
+  if (x.wts) return launch_avgprof(i16_cube<BS, true>{x, E1, (unsigned)L}, E, L, n, csum, out, stride, st);
+  return launch_avgprof(i16_cube<BS, false>{x, E1, (unsigned)L}, E, L, n, csum, out, stride, st);
+}
+hipError_t launch_pfd_avgprof_i16(const PfdI16Src& x, int npart, int nsub, int L, int64_t n,
+                                  double* csum, double* out, int64_t stride, hipStream_t st) {
+  const int64_t E1 = (int64_t)nsub * L, E = E1 * npart;
+  if (E1 < 1 || E1 > 0x7fffffff - PFD_AVG_CHUNK) return hipErrorInvalidValue;  // i16_cursor's 32 bits
+  return x.bswap ? launch_avgprof_i16<true>(x, (unsigned)E1, E, L, n, csum, out, stride, st)
+                 : launch_avgprof_i16<false>(x, (unsigned)E1, E, L, n, csum, out, stride, st);
 }
 
 }  // namespace pfe

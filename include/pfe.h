@@ -625,6 +625,82 @@ int pfe_pfd_subband3_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, u
 int pfe_pfd_avgprof_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, int64_t out_stride,
                         uint32_t flags);
 
+/* ---- kill masks: killed intervals and sub-bands of a fold --------------------------------
+ * PRESTO's pfd class re-scores a fold after RFI excision with kill_intervals() and
+ * kill_subbands() (show_pfd -killparts ... -killsubs ...): the rows of the cube are zeroed and
+ * sumprof, avgprof and varprof recomputed.  The _kill calls score such a fold where it lies: the
+ * cube is read once, as the values it holds, and a value of a killed part (sub-integration) or
+ * sub-band is selected away where it is loaded.  No zapped copy of the cube is made.
+ *
+ * Contract: every output and the status of a _kill call is, bit for bit, that of the plain call
+ * of the same name on the cube z, with the same subfreqs, scal, options and other flags.
+ *   z[i][p][s][b] = (parts[i][p] || subs[i][s]) ? +0.0 : x[i][p][s][b]
+ * is numpy's np.where(kill, 0.0, x).  A float32 cube is widened first.
+ *
+ * A killed value is replaced, never multiplied: a NaN, +-inf or a huge value in a killed row
+ * reaches no sum.  This differs from PRESTO's `*= 0.0` only for non-finite values (NaN * 0 and
+ * inf * 0 are NaN there) and for the sign of zero (a negative value times 0.0 is -0.0 there, +0.0
+ * here).  The caller's cube and masks are never written.  A NaN that is not killed is a NaN;
+ * which payload survives is unspecified, as for PFE_FLAG_PFD_BSWAP.  scal[PFE_PFD_AVGPROF] and
+ * scal[PFE_PFD_VARPROF] stay the caller's: they must be those of the zapped fold.  With
+ * PFE_FLAG_PFD_AVGPROF the average is derived from z: numpy's (z / proflen).sum() in memory
+ * order, by the rule of pfe_pfd_avgprof -- the zeros sit where the killed values were, inside
+ * the 8192-value chunks and the pairwise leaves.  pfe_pfd_avgprof_kill gives that value alone.
+ *
+ * Masks: parts n x npart and subs n x nsub bytes, dense, non-zero = killed; host or device
+ * pointers as PFE_FLAG_DEVICE_PTRS says for every array.  kill == NULL, or both members NULL:
+ * the call is the plain call -- the same kernels, the same scratch, the same bits.  One member
+ * NULL: nothing of that kind is killed.  The f64 forms accept PFE_FLAG_PFD_BSWAP: the word is
+ * reversed, then selected.  All forms accept PFE_FLAG_PFD_AVGPROF.  The parts of an element are
+ * summed in fp64, S[s][b] = z[0][s][b] + z[1][s][b] + ... + z[npart-1][s][b], in that order from
+ * the value of part 0, and the f64 kernels run on S as folds of one part (the float32 path).
+ * A fold with every part or every sub-band killed is the zero cube.
+ *
+ * Everything else -- shape limits, status bits, stream behaviour, the routing options -- is that
+ * of the plain call of the same name; PFE_EINVAL texts go under the _kill name.
+ * Scratch: a masked call, f64 included, runs in passes of `chunk` folds by the rule of the
+ * float32 calls (PFE_OPT_PFD_F32_CHUNK governs this path too): the arrays a host-pointer call
+ * stages (the cube as the values it holds, subfreqs, scal, then directly behind scal parts and
+ * subs, each only when given, then the outputs; pfe_pfd_avgprof_kill: the cube, parts, subs, the
+ * n results), then chunk x nsub x proflen doubles of part sums, then the scratch of the f64 call
+ * on `chunk` folds.
+ *
+ * There are no _i16 forms: an int16 cube carries a weight per (part, sub-band), and a weight of
+ * 0 is the kill.  Not offered: per-element masks, and weights for float cubes. */
+typedef struct pfe_pfd_kill {
+  const uint8_t* parts; /* n x npart, non-zero = killed; NULL = none */
+  const uint8_t* subs;  /* n x nsub,  non-zero = killed; NULL = none */
+} pfe_pfd_kill;
+
+int pfe_pfd_dmprof_kill(pfe_handle* h, const pfe_pfd_in* in, const pfe_pfd_kill* kill,
+                        double* profile, float* chis, double* lyon8, uint32_t* status,
+                        uint32_t flags);
+int pfe_pfd_bates22_kill(pfe_handle* h, const pfe_pfd_in* in, const pfe_pfd_kill* kill, double* out,
+                         uint32_t* status, uint32_t flags);
+int pfe_pfd_params4_kill(pfe_handle* h, const pfe_pfd_in* in, const pfe_pfd_kill* kill, double* out,
+                         uint32_t* status, uint32_t flags);
+int pfe_pfd_dmfit4_kill(pfe_handle* h, const pfe_pfd_in* in, const pfe_pfd_kill* kill, double* out,
+                        uint32_t* status, uint32_t flags);
+int pfe_pfd_subband3_kill(pfe_handle* h, const pfe_pfd_in* in, const pfe_pfd_kill* kill, double* out,
+                          uint32_t* status, uint32_t flags);
+int pfe_pfd_avgprof_kill(pfe_handle* h, const double* profs, int32_t npart, int32_t nsub,
+                         int32_t proflen, int64_t n, const pfe_pfd_kill* kill, double* out,
+                         int64_t out_stride, uint32_t flags);
+int pfe_pfd_dmprof_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe_pfd_kill* kill,
+                            double* profile, float* chis, double* lyon8, uint32_t* status,
+                            uint32_t flags);
+int pfe_pfd_bates22_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe_pfd_kill* kill,
+                             double* out, uint32_t* status, uint32_t flags);
+int pfe_pfd_params4_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe_pfd_kill* kill,
+                             double* out, uint32_t* status, uint32_t flags);
+int pfe_pfd_dmfit4_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe_pfd_kill* kill,
+                            double* out, uint32_t* status, uint32_t flags);
+int pfe_pfd_subband3_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe_pfd_kill* kill,
+                              double* out, uint32_t* status, uint32_t flags);
+int pfe_pfd_avgprof_kill_f32(pfe_handle* h, const float* profs, int32_t npart, int32_t nsub,
+                             int32_t proflen, int64_t n, const pfe_pfd_kill* kill, double* out,
+                             int64_t out_stride, uint32_t flags);
+
 /* ---- float32 candidates: the float-array calls on arrays of floats ----------------------
  * A candidate that never was a .pfd or .phcx file -- a float32 tensor from a GPU folder or a
  * normalising step, the arrays an ML pipeline keeps, the float32 DM curve pfe_pfd_dmprof

@@ -74,6 +74,18 @@ EXPORTED_SYMBOLS = (
     "pfe_pfd_dmfit4_i16",
     "pfe_pfd_subband3_i16",
     "pfe_pfd_avgprof_i16",
+    "pfe_pfd_dmprof_kill",
+    "pfe_pfd_bates22_kill",
+    "pfe_pfd_params4_kill",
+    "pfe_pfd_dmfit4_kill",
+    "pfe_pfd_subband3_kill",
+    "pfe_pfd_avgprof_kill",
+    "pfe_pfd_dmprof_kill_f32",
+    "pfe_pfd_bates22_kill_f32",
+    "pfe_pfd_params4_kill_f32",
+    "pfe_pfd_dmfit4_kill_f32",
+    "pfe_pfd_subband3_kill_f32",
+    "pfe_pfd_avgprof_kill_f32",
 )
 PFE_FLAG_PFD_AVGPROF = 0x2  # PFD calls: derive scal[:, PFE_PFD_AVGPROF] from the cube
 PFE_FLAG_PFD_BSWAP = 0x4    # f64 and int16 PFD calls: the cube (int16: and scl, offs, wts) byte-reversed
@@ -193,6 +205,12 @@ class PfdI16In(C.Structure):
     ]
 
 
+class PfdKill(C.Structure):
+    """pfe_pfd_kill: the killed parts (n x npart) and sub-bands (n x nsub) of a batch of folds,
+    one byte each, non-zero = killed; either may be null."""
+    _fields_ = [("parts", C.c_void_p), ("subs", C.c_void_p)]
+
+
 class PhcxInfo(C.Structure):
     _fields_ = [
         ("status", C.c_int32),
@@ -278,6 +296,10 @@ def load_library(path: str | None = None) -> C.CDLL:
         bates_f64 = [vp, ptr(BatesF64In), vp, vp, u32]
         bates_f32 = [vp, ptr(BatesF32In), vp, vp, u32]
         avg = [vp, vp, i32, i32, i32, i64, vp, i64, u32]
+        kill = ptr(PfdKill)
+        pfd_kill = [vp, ptr(PfdIn), kill, vp, vp, u32]
+        pfd_kill_f32 = [vp, ptr(PfdF32In), kill, vp, vp, u32]
+        avg_kill = [vp, vp, i32, i32, i32, i64, kill, vp, i64, u32]
         signatures = {  # name: (restype, argtypes), as include/pfe.h and include/pfe_io.h declare
             "pfe_abi_version": (rc, []), "pfe_device_count": (rc, []),
             "pfe_create": (rc, [C.c_int, ptr(vp)]), "pfe_destroy": (None, [vp]),
@@ -305,6 +327,13 @@ def load_library(path: str | None = None) -> C.CDLL:
             "pfe_pfd_bates22_i16": (rc, pfd_i16), "pfe_pfd_params4_i16": (rc, pfd_i16),
             "pfe_pfd_dmfit4_i16": (rc, pfd_i16), "pfe_pfd_subband3_i16": (rc, pfd_i16),
             "pfe_pfd_avgprof_i16": (rc, [vp, ptr(PfdI16In), vp, i64, u32]),
+            "pfe_pfd_dmprof_kill": (rc, [vp, ptr(PfdIn), kill, vp, vp, vp, vp, u32]),
+            "pfe_pfd_bates22_kill": (rc, pfd_kill), "pfe_pfd_params4_kill": (rc, pfd_kill),
+            "pfe_pfd_dmfit4_kill": (rc, pfd_kill), "pfe_pfd_subband3_kill": (rc, pfd_kill),
+            "pfe_pfd_dmprof_kill_f32": (rc, [vp, ptr(PfdF32In), kill, vp, vp, vp, vp, u32]),
+            "pfe_pfd_bates22_kill_f32": (rc, pfd_kill_f32), "pfe_pfd_params4_kill_f32": (rc, pfd_kill_f32),
+            "pfe_pfd_dmfit4_kill_f32": (rc, pfd_kill_f32), "pfe_pfd_subband3_kill_f32": (rc, pfd_kill_f32),
+            "pfe_pfd_avgprof_kill": (rc, avg_kill), "pfe_pfd_avgprof_kill_f32": (rc, avg_kill),
             "pfe_phcx_parse": (rc, [ptr(C.c_char_p), i64, i32, i32, ptr(vp)]),
             "pfe_phcx_count": (i64, [vp]),
             "pfe_phcx_info_get": (rc, [vp, i64, ptr(PhcxInfo)]),
@@ -891,22 +920,70 @@ class Engine:
         pin = (PfdF32In if f32 else PfdIn)(_ptr(profs), _ptr(subfreqs), _ptr(scal), npart, nsub, L, n)
         return pin, dev, (profs, subfreqs, scal)
 
-    def _pfd_fn(self, fn, pin):
+    def _pfd_fn(self, fn, pin, kill=None):
         """The C entry point of a PFD call: its _f32 form for a float32 cube, its _i16 form for
-        an int16 one."""
+        an int16 one; with masks (kill: a PfdKill) its _kill form, the masks behind `in`."""
         sfx = "_f32" if isinstance(pin, PfdF32In) else "_i16" if isinstance(pin, PfdI16In) else ""
-        return getattr(self.lib, "pfe_" + fn + sfx)
+        if kill is None:
+            return getattr(self.lib, "pfe_" + fn + sfx)
+        f = getattr(self.lib, "pfe_" + fn + "_kill" + sfx)
+        return lambda h, pin_ref, *rest: f(h, pin_ref, C.byref(kill), *rest)
 
-    def pfd_avgprof(self, profs, byteswapped=False, scl=None, offs=None, wts=None):
+    def _pfd_kill(self, fn, profs, kill_parts, kill_subs):
+        """The masks of a PFD call -> (PfdKill or None when both are None, the arrays it points
+        into).  kill_parts (n,npart) and kill_subs (n,nsub), bool or uint8, non-zero = killed; a
+        1-D mask is broadcast to every fold.  numpy arrays for a host cube, torch.bool /
+        torch.uint8 tensors on the cube's device for a device cube."""
+        if kill_parts is None and kill_subs is None:
+            return None, None
+        if profs.ndim != 4:
+            raise ValueError(f"{fn}: profs must be (n,npart,nsub,L)")
+        if self._is_i16(profs):
+            raise ValueError(f"{fn}: kill_parts and kill_subs are for float cubes; an int16 cube "
+                             "is zapped through wts (a weight of 0 is the kill)")
+        n, npart, nsub, _ = profs.shape
+        dev = _is_device(profs)
+        keep = []
+        for name, m, width in (("kill_parts", kill_parts, npart), ("kill_subs", kill_subs, nsub)):
+            if m is None:
+                keep.append(None)
+                continue
+            if dev:
+                import torch
+
+                if not isinstance(m, torch.Tensor) or not m.is_cuda or m.device != profs.device:
+                    raise TypeError(f"{fn}: {name}: expected a tensor on the cube's device")
+                if m.dtype not in (torch.bool, torch.uint8):
+                    raise ValueError(f"{fn}: {name} must be torch.bool or torch.uint8")
+                if tuple(m.shape) not in ((width,), (n, width)):
+                    raise ValueError(f"{fn}: {name} must be ({width},) or (n,{width}) = {(n, width)}")
+                m = m.expand(n, width).contiguous()
+                keep.append(m.view(torch.uint8) if m.dtype == torch.bool else m)
+            else:
+                m = np.asarray(m)
+                if m.dtype not in (np.bool_, np.uint8):
+                    raise ValueError(f"{fn}: {name} must be bool or uint8")
+                if m.shape not in ((width,), (n, width)):
+                    raise ValueError(f"{fn}: {name} must be ({width},) or (n,{width}) = {(n, width)}")
+                keep.append(np.ascontiguousarray(np.broadcast_to(m, (n, width))).view(np.uint8))
+        kill = PfdKill(_ptr(keep[0]) if keep[0] is not None else None,
+                       _ptr(keep[1]) if keep[1] is not None else None)
+        return kill, keep
+
+    def pfd_avgprof(self, profs, byteswapped=False, scl=None, offs=None, wts=None,
+                    kill_parts=None, kill_subs=None):
         """numpy's (profs / proflen).sum() of each fold of a (n,npart,nsub,L) cube, bit for
         bit (pfe_pfd_avgprof; a float32 cube -- numpy array or device tensor -- goes to
         pfe_pfd_avgprof_f32 as it is and gives the value of profs.astype(float64)): the
         scal[:, 2] every PFD call reads.  byteswapped: as in pfd_dmprof.  An int16 cube with scl,
         offs (and wts) as in pfd_dmprof goes to pfe_pfd_avgprof_i16 and gives the value of the
-        decoded cube.  Returns (n,) float64 where the cube lives."""
+        decoded cube.  kill_parts, kill_subs: as in pfd_dmprof; the value is that of the zapped
+        cube np.where(kill, 0.0, profs) (pfe_pfd_avgprof_kill).  Returns (n,) float64 where the
+        cube lives."""
         if profs.ndim != 4:
             raise ValueError("pfd_avgprof: profs must be (n,npart,nsub,L)")
         n, npart, nsub, L = profs.shape
+        kill, kkeep = self._pfd_kill("pfd_avgprof", profs, kill_parts, kill_subs)
         if self._is_i16(profs):
             arrs = self._pfd_i16_arrays("pfd_avgprof", profs, scl, offs, wts)
             if _is_device(profs):
@@ -942,12 +1019,18 @@ class Engine:
             flags = 0
         if byteswapped:
             flags |= PFE_FLAG_PFD_BSWAP
+        if kill is not None:
+            fn = self.lib.pfe_pfd_avgprof_kill_f32 if f32 else self.lib.pfe_pfd_avgprof_kill
+            self._check(fn(self._h, _ptr(profs), npart, nsub, L, n, C.byref(kill), _ptr(out), 1, flags))
+            del kkeep
+            return out
         fn = self.lib.pfe_pfd_avgprof_f32 if f32 else self.lib.pfe_pfd_avgprof
         self._check(fn(self._h, _ptr(profs), npart, nsub, L, n, _ptr(out), 1, flags))
         return out
 
     def pfd_dmprof(self, profs, subfreqs, scal, profile=True, chis=True, lyon8=True,
-                   derive_avgprof=False, byteswapped=False, scl=None, offs=None, wts=None):
+                   derive_avgprof=False, byteswapped=False, scl=None, offs=None, wts=None,
+                   kill_parts=None, kill_subs=None):
         """PFD preprocessing + Lyon features (pfe_pfd_dmprof) for a batch of folds of one
         shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL).
         A float32 cube (numpy array or device tensor) is scored as it is, by the _f32 call of
@@ -967,7 +1050,16 @@ class Engine:
         fold and one part stride in bytes shared by all); byteswapped then says that the int16
         and the float32 values are all byte-reversed.  Giving them with any other cube is a
         ValueError.
+        kill_parts, kill_subs (this and the other PFD methods, f64 and float32 cubes): killed
+        sub-integrations (n,npart) and sub-bands (n,nsub), bool or uint8, non-zero = killed, a 1-D
+        mask for every fold alike; numpy arrays with a host cube, torch.bool / torch.uint8 tensors
+        on the cube's device with a device cube.  The fold is scored by the _kill call where it
+        lies: the bits of the plain call on np.where(kill, 0.0, profs), no copy of the cube made.
+        scal[:, 2] and scal[:, 3] must be those of the zapped fold (pfd.varprof; derive_avgprof
+        derives the average of the zapped cube).  With an int16 cube they are a ValueError: there
+        wts = 0 is the kill.  Both None: the plain call.
         Returns dict(profile (n,L) f64, chis (n,100) f32, lyon8 (n,8) f64, status (n,))."""
+        kill, kkeep = self._pfd_kill("pfd_dmprof", profs, kill_parts, kill_subs)
         pin, dev, keep = self._pfd_args(profs, subfreqs, scal, "pfd_dmprof", scl, offs, wts)
         n, L = pin.n, pin.proflen
         out = {}
@@ -989,51 +1081,57 @@ class Engine:
         out["chis"] = mk((n, PFE_PFD_NDM), f32) if chis else None
         out["lyon8"] = mk((n, 8), f64) if lyon8 else None
         out["status"] = mk((n,), i32)
-        self._check(self._pfd_fn("pfd_dmprof", pin)(
+        self._check(self._pfd_fn("pfd_dmprof", pin, kill)(
             self._h, C.byref(pin), _ptr(out["profile"]) if profile else None,
             _ptr(out["chis"]) if chis else None, _ptr(out["lyon8"]) if lyon8 else None,
             _ptr(out["status"]), flags))
-        del keep
+        del keep, kkeep
         return out
 
     def _pfd_scores(self, fn, k, profs, subfreqs, scal, out, status, derive_avgprof=False,
-                    byteswapped=False, scl=None, offs=None, wts=None):
+                    byteswapped=False, scl=None, offs=None, wts=None, kill_parts=None,
+                    kill_subs=None):
+        kill, kkeep = self._pfd_kill(fn, profs, kill_parts, kill_subs)
         pin, dev, keep = self._pfd_args(profs, subfreqs, scal, fn, scl, offs, wts)
         out, status, flags = self._outputs(dev, profs, pin.n, k, out, status)
         if derive_avgprof:
             flags |= PFE_FLAG_PFD_AVGPROF
         if byteswapped:
             flags |= PFE_FLAG_PFD_BSWAP
-        self._check(self._pfd_fn(fn, pin)(self._h, C.byref(pin), _ptr(out), _ptr(status), flags))
-        del keep
+        self._check(self._pfd_fn(fn, pin, kill)(self._h, C.byref(pin), _ptr(out), _ptr(status), flags))
+        del keep, kkeep
         return out, status
 
     def pfd_bates22(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
-                    byteswapped=False, scl=None, offs=None, wts=None):
+                    byteswapped=False, scl=None, offs=None, wts=None, kill_parts=None,
+                    kill_subs=None):
         """The 22 scores of PFD folds (pfe_pfd_bates22, PFDFile.compute) for a batch of one
         shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL) with
         scal[:, 7] = bary_p1.  Returns (out (n,22) f64, status (n,))."""
         return self._pfd_scores("pfd_bates22", 22, profs, subfreqs, scal, out, status,
-                                derive_avgprof, byteswapped, scl, offs, wts)
+                                derive_avgprof, byteswapped, scl, offs, wts, kill_parts, kill_subs)
 
     # one score group of a batch of folds (PFDOperations; inputs as pfd_bates22)
     def pfd_params4(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
-                    byteswapped=False, scl=None, offs=None, wts=None):
+                    byteswapped=False, scl=None, offs=None, wts=None, kill_parts=None,
+                    kill_subs=None):
         """getCandidateParameters (pfe_pfd_params4): [period_ms, snr, dm, width], unfiltered."""
         return self._pfd_scores("pfd_params4", 4, profs, subfreqs, scal, out, status,
-                                derive_avgprof, byteswapped, scl, offs, wts)
+                                derive_avgprof, byteswapped, scl, offs, wts, kill_parts, kill_subs)
 
     def pfd_dmfit4(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
-                   byteswapped=False, scl=None, offs=None, wts=None):
+                   byteswapped=False, scl=None, offs=None, wts=None, kill_parts=None,
+                   kill_subs=None):
         """getDMFittings (pfe_pfd_dmfit4): [s16, s17, Shift (signed), s19]."""
         return self._pfd_scores("pfd_dmfit4", 4, profs, subfreqs, scal, out, status,
-                                derive_avgprof, byteswapped, scl, offs, wts)
+                                derive_avgprof, byteswapped, scl, offs, wts, kill_parts, kill_subs)
 
     def pfd_subband3(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
-                     byteswapped=False, scl=None, offs=None, wts=None):
+                     byteswapped=False, scl=None, offs=None, wts=None, kill_parts=None,
+                     kill_subs=None):
         """getSubbandParameters (pfe_pfd_subband3): s20-s22."""
         return self._pfd_scores("pfd_subband3", 3, profs, subfreqs, scal, out, status,
-                                derive_avgprof, byteswapped, scl, offs, wts)
+                                derive_avgprof, byteswapped, scl, offs, wts, kill_parts, kill_subs)
 
 
 class PhcxBatch:
@@ -1185,7 +1283,8 @@ class PfdBatch:
             periods=self.fetch(i, PFE_PFD_F_PERIODS, int(inf["numperiods"])),
             pdots=self.fetch(i, PFE_PFD_F_PDOTS, int(inf["numpdots"])), profs=profs,
             stats=self.fetch(i, PFE_PFD_F_STATS, npart * nsub * 7).reshape(npart, nsub, 7),
-            subfreqs=self.fetch(i, PFE_PFD_F_SUBFREQS, nsub), avgprof=None, **kw)
+            subfreqs=self.fetch(i, PFE_PFD_F_SUBFREQS, nsub), avgprof=None, killed_subbands=[],
+            killed_intervals=[], **kw)
 
     def pack(self, rows, shape, threads: int = 0, alloc=None, cube=True):
         """Dense inputs of the PFD calls for the given rows (all of one (npart, nsub, proflen)

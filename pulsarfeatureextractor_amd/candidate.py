@@ -290,12 +290,54 @@ class PFDFile(CandidateFileInterface):
     def _batch(self):
         return _pfd.batch_inputs([self.data])
 
+    def _kill(self):
+        """Keywords of the PFD calls for the killed rows: the masks, and the average derived
+        from the zapped cube on the device ({}: nothing killed, the plain calls)."""
+        return self.profileOps._kill(self.data)
+
+    # killed intervals and sub-bands, as PRESTO's pfd class keeps them (PFDFile.py:183-184 makes
+    # the lists, calc_varprof :314-326 skips them).  The cube self.data.profs is not modified:
+    # the library selects the killed rows away where it loads them (the pfe_pfd_*_kill calls)
+    @property
+    def killed_intervals(self):
+        return self.data.killed_intervals
+
+    @property
+    def killed_subbands(self):
+        return self.data.killed_subbands
+
+    def calc_varprof(self):
+        """:314-326 -- the sum of the prof_var foldstats over the rows that are not killed."""
+        parts, subs = _pfd.kill_masks([self.data])
+        return float(_pfd.varprof(self.data.stats[:, :, 5], None if parts is None else parts[0],
+                                  None if subs is None else subs[0]))
+
+    def _killed(self, kept, new, limit, what):
+        new = [int(i) for i in new]
+        for i in new:
+            if not 0 <= i < limit:
+                raise IndexError(f"{what} {i} out of range: the fold has {limit}")
+        kept.extend(i for i in new if i not in kept)
+        if not (self.data.killed_intervals or self.data.killed_subbands):
+            return  # an empty list on a fold with nothing killed: nothing changes
+        self.data.varprof = self.calc_varprof()
+        self.data.avgprof = None  # derived from the zapped cube on the device
+        self._dmp = None
+
+    def kill_intervals(self, intervals):
+        """PRESTO's pfd.kill_intervals: sub-integrations that every later score leaves out."""
+        self._killed(self.data.killed_intervals, intervals, self.data.npart, "interval")
+
+    def kill_subbands(self, subbands):
+        """PRESTO's pfd.kill_subbands: sub-bands that every later score leaves out."""
+        self._killed(self.data.killed_subbands, subbands, self.data.nsub, "sub-band")
+
     def _dmprof(self):
         """pfe_pfd_dmprof of this fold (profile, chi^2 curve, Lyon features), launched once
         and shared by the profile / DM-curve / stat-score calls."""
         if getattr(self, "_dmp", None) is None:
             profs, subfreqs, scal = self._batch()
-            self._dmp = self.engine.pfd_dmprof(profs, subfreqs, scal)
+            self._dmp = self.engine.pfd_dmprof(profs, subfreqs, scal, **self._kill())
         return self._dmp
 
     def isValid(self):
@@ -306,7 +348,7 @@ class PFDFile(CandidateFileInterface):
 
     def compute(self):
         """PFDFile.compute (:587-613): the 22 scores."""
-        out, st = self.engine.pfd_bates22(*self._batch())
+        out, st = self.engine.pfd_bates22(*self._batch(), **self._kill())
         msg = status_error(int(st[0]))
         if msg:
             raise Exception(msg)

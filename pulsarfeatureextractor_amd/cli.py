@@ -3,6 +3,7 @@
   python -m pulsarfeatureextractor_amd.cli -c <dir|file> -o <out> [--phcx|--superb]
          [--arff] [--profile] [--dmprof] [-v] [--device N] [--workers K] [--start K]
          [--metrics FILE] [--gpus N [--devices D0,D1,...]]
+         [--pfd --killsubs LIST --killparts LIST]
 
 Same flags, same output-file probing (:147-160), same mode dispatch (:215-290), for PHCX,
 SUPERB and PFD files in every mode, --label included (its prompt is commented out in the
@@ -15,6 +16,7 @@ import sys
 from optparse import OptionParser
 
 from . import processor
+from .pfd import parse_kill_list
 
 
 def main(argv=None):
@@ -44,7 +46,22 @@ def main(argv=None):
     # structured per-run metrics (not in the reference): one JSON object written to FILE at
     # the end of the run (candidates, successes, failures by reason, candidates/s, times)
     p.add_option("--metrics", action="store", dest="metrics", type="string", default=None)
+    # show_pfd's -killsubs / -killparts (not in the reference's command line): sub-bands and
+    # sub-integrations left out of every fold of a --pfd run, e.g. "0,3:5" = 0, 3, 4, 5
+    p.add_option("--killsubs", action="store", dest="killsubs", type="string", default=None)
+    p.add_option("--killparts", action="store", dest="killparts", type="string", default=None)
     args, _ = p.parse_args(argv)
+    kill = {}
+    for opt, key in (("killsubs", "kill_subbands"), ("killparts", "kill_intervals")):
+        text = getattr(args, opt)
+        if text is None:
+            continue
+        if not args.pfd or args.phcx or args.superb:
+            p.error(f"--{opt} is for --pfd runs only")
+        try:
+            kill[key] = parse_kill_list(text)
+        except ValueError as e:
+            p.error(f"--{opt}: {e}")
     # output-file probing (:147-160)
     single_file = os.path.exists(args.outputPath)
     if not single_file:
@@ -69,7 +86,7 @@ def main(argv=None):
     # else: the parent never initialises a GPU -- each shard worker is a spawned process that
     # opens its own device (processor.DataProcessor._run_shards)
     dp = processor.DataProcessor(args.verbose, workers=args.workers, start=args.start,
-                                 metrics_path=args.metrics, gpus=args.gpus, devices=devices)
+                                 metrics_path=args.metrics, gpus=args.gpus, devices=devices, **kill)
     phcx, pfd, superb = args.phcx, args.pfd, args.superb
     try:
         if args.label:  # :220-225 (labelPFD with the two arguments ScoreGenerator passes)

@@ -1042,6 +1042,35 @@ static int pfd_i16_check(pfe_handle* h, const char* fn, const pfe_pfd_i16_in* f,
                    fn, (long long)fs, f->npart, (long long)ps);
   return PFE_OK;
 }
+// The masks of a _kill call.  kill == NULL, or both members NULL: the call is the plain call
+static bool pfd_killed(const pfe_pfd_kill* kill) { return kill && (kill->parts || kill->subs); }
+static pfe::PfdKillSrc pfd_kill_src(const pfe_pfd_kill* kill) {
+  pfe::PfdKillSrc k;
+  k.parts = kill->parts;
+  k.subs = kill->subs;
+  return k;
+}
+// host path: the masks into their regions behind scal, and `k` reads them there
+static int stage_kill(pfe_handle* h, pfe::PfdKillSrc& k, uint8_t* dparts, uint8_t* dsubs, int64_t n,
+                      int npart, int nsub) {
+  int rc;
+  if (k.parts) {
+    if ((rc = stage_in(h, dparts, k.parts, (size_t)n * npart))) return rc;
+    k.parts = dparts;
+  }
+  if (k.subs) {
+    if ((rc = stage_in(h, dsubs, k.subs, (size_t)n * nsub))) return rc;
+    k.subs = dsubs;
+  }
+  return PFE_OK;
+}
+// the cube of a masked pass from its value `at` on, and the form of its values
+static const void* pfd_kill_cube(const pfe::PfdArgs& a, const float* x32, int64_t at) {
+  return x32 ? static_cast<const void*>(x32 + at) : static_cast<const void*>(a.profs + at);
+}
+static int pfd_kill_elem(const float* x32, bool be) {
+  return x32 ? pfe::PFD_KILL_F32 : be ? pfe::PFD_KILL_BE64 : pfe::PFD_KILL_F64;
+}
 // a null or misaligned cube, in the words of the f64 call
 static int pfd_cube_check(pfe_handle* h, const char* fn, const pfe_pfd_in* in, bool f32,
                           const float* x32, uint32_t flags) {
@@ -1057,17 +1086,23 @@ static int pfd_cube_check(pfe_handle* h, const char* fn, const pfe_pfd_in* in, b
 // call, whose part sums k_pfd_partsum_f32 forms in psum first, for the f64 kernels to read as
 // folds of one part; one pass of a PFE_FLAG_PFD_BSWAP call (be: a.profs holds the words),
 // whose part sums k_pfd_partsum_be64 forms; one pass of an _i16 call (q: its arrays on the
-// device), whose values k_pfd_partsum_i16 decodes and sums.  Outputs are moved by the caller.
+// device), whose values k_pfd_partsum_i16 decodes and sums; one pass of a _kill call (km: its
+// masks on the device, the cube in x32 or a.profs), whose selected values k_pfd_partsum_kill
+// sums, with the masks of the pass's first fold.  Outputs are moved by the caller.
 static int pfd_pass(pfe_handle* h, const char* fn, const pfe::PfdArgs& a, const float* x32, bool be,
-                    const pfe::PfdI16Src* q, double* psum, int64_t c0, int64_t cn, pfe::PfdArgs& b) {
+                    const pfe::PfdI16Src* q, double* psum, int64_t c0, int64_t cn, pfe::PfdArgs& b,
+                    const pfe::PfdKillSrc* km = nullptr) {
   b = a;
   b.n = cn;
   b.subfreqs = a.subfreqs + c0 * a.nsub;
   b.scal = a.scal + c0 * PFE_PFD_NSCAL;
-  if (!x32 && !be && !q) return PFE_OK;  // c0 = 0, cn = n
+  if (!x32 && !be && !q && !km) return PFE_OK;  // c0 = 0, cn = n
   const int64_t at = c0 * a.npart * (int64_t)a.nsub * a.L;
   hipError_t e =
-      q    ? pfe::launch_pfd_partsum_i16(q->from(c0), psum, a.npart, a.nsub, a.L, cn, h->stream)
+      km   ? pfe::launch_pfd_partsum_kill(pfd_kill_cube(a, x32, at), pfd_kill_elem(x32, be),
+                                          km->from(c0, a.npart, a.nsub), psum, a.npart, a.nsub, a.L,
+                                          cn, h->stream)
+      : q  ? pfe::launch_pfd_partsum_i16(q->from(c0), psum, a.npart, a.nsub, a.L, cn, h->stream)
       : be ? pfe::launch_pfd_partsum_be64(a.profs + at, psum, a.npart, a.nsub, a.L, cn, h->stream)
            : pfe::launch_pfd_partsum_f32(x32 + at, psum, a.npart, a.nsub, a.L, cn, h->stream);
   if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
@@ -1092,14 +1127,18 @@ static int pfd_avg_begin(pfe_handle* h, const pfe_pfd_in* in, double* staged,
 }
 // the averages of folds [c0, c0 + cn) of the batch `a` into their rows of wscal, from the cube
 // as the call holds it on the device (x32: the floats of an _f32 call; be: the byte-reversed
-// words of a PFE_FLAG_PFD_BSWAP call; q: the arrays of an _i16 call)
+// words of a PFE_FLAG_PFD_BSWAP call; q: the arrays of an _i16 call; km: the masks of a _kill
+// call, whose average is that of the zapped cube)
 static int pfd_avg_pass(pfe_handle* h, const char* fn, const pfe::PfdArgs& a, const float* x32,
                         bool be, const pfe::PfdI16Src* q, int64_t c0, int64_t cn, double* csum,
-                        double* wscal) {
+                        double* wscal, const pfe::PfdKillSrc* km = nullptr) {
   const int64_t E = (int64_t)a.npart * a.nsub * a.L;
   double* out = wscal + c0 * PFE_PFD_NSCAL + PFE_PFD_AVGPROF;
   const hipError_t e =
-      q    ? pfe::launch_pfd_avgprof_i16(q->from(c0), a.npart, a.nsub, a.L, cn, csum, out, PFE_PFD_NSCAL,
+      km   ? pfe::launch_pfd_avgprof_kill(pfd_kill_cube(a, x32, c0 * E), pfd_kill_elem(x32, be),
+                                          km->from(c0, a.npart, a.nsub), a.npart, a.nsub, a.L, cn,
+                                          csum, out, PFE_PFD_NSCAL, h->stream)
+      : q  ? pfe::launch_pfd_avgprof_i16(q->from(c0), a.npart, a.nsub, a.L, cn, csum, out, PFE_PFD_NSCAL,
                                          h->stream)
       : x32 ? pfe::launch_pfd_avgprof_f32(x32 + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL, h->stream)
       : be ? pfe::launch_pfd_avgprof_be64(a.profs + c0 * E, E, a.L, cn, csum, out, PFE_PFD_NSCAL,
@@ -1110,12 +1149,14 @@ static int pfd_avg_pass(pfe_handle* h, const char* fn, const pfe::PfdArgs& a, co
 }
 
 // pfe_pfd_dmprof, pfe_pfd_dmprof_f32 (f32: the cube is x32, in->profs is not read) and
-// pfe_pfd_dmprof_i16 (i16: the caller's struct; q: its arrays, in->profs is not read)
+// pfe_pfd_dmprof_i16 (i16: the caller's struct; q: its arrays, in->profs is not read), and the
+// _kill forms of the first two (kcall; kill: the caller's masks, or null)
 static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const float* x32,
                            double* profile, float* chis, double* lyon8, uint32_t* status,
                            uint32_t flags, const pfe_pfd_i16_in* i16 = nullptr,
-                           pfe::PfdI16Src* q = nullptr) {
-  const char* fn = q ? "pfd_dmprof_i16" : "pfd_dmprof";
+                           pfe::PfdI16Src* q = nullptr, bool kcall = false,
+                           const pfe_pfd_kill* kill = nullptr) {
+  const char* fn = q ? "pfd_dmprof_i16" : kcall ? "pfd_dmprof_kill" : "pfd_dmprof";
   int64_t n;
   int rc = call_check(h, fn, in, status != nullptr, n);
   if (rc || n == 0) return rc;
@@ -1129,7 +1170,11 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   if ((rc = call_begin(h))) return rc;
   // folds per pass: all of them, or what the part sums of a float32, byte-reversed or int16
   // cube allow (an int16 call deals with the byte order in its own kernels)
-  const bool be = !q && (flags & PFE_FLAG_PFD_BSWAP), sums = f32 || be || q;
+  const bool be = !q && (flags & PFE_FLAG_PFD_BSWAP), killed = pfd_killed(kill);
+  const bool sums = f32 || be || q || killed;
+  pfe::PfdKillSrc kmask;
+  if (killed) kmask = pfd_kill_src(kill);
+  const pfe::PfdKillSrc* km = killed ? &kmask : nullptr;
   const int ki = !q ? pfe::PFD_I16_NONE : q->wts ? pfe::PFD_I16_WEIGHTS : pfe::PFD_I16_PLAIN;
   const int64_t pass =
       sums ? pfe::pfd_f32_chunk(in->nsub, in->proflen, n, h->opt.pfd_f32_chunk) : n;
@@ -1152,9 +1197,11 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   pfe::PfdDmprofStage s;
   rc = lay_out(h, s, [&](pfe::Arena& A) {
     return pfe::pfd_dmprof_layout(A, *in, host, profile, chis, lyon8, ws_bytes, sums ? pass : 0,
-                                  derive, be, ki);
+                                  derive, be || (killed && !f32), ki, kmask.mask());
   });
   if (rc || (host && (rc = stage_pfd(h, in, x32, q, s.in, a)))) return rc;
+  if (host && killed && (rc = stage_kill(h, kmask, s.in.kparts, s.in.ksubs, n, in->npart, in->nsub)))
+    return rc;
   double* wscal = nullptr;
   if (derive && (rc = pfd_avg_begin(h, in, host ? s.in.scal : nullptr, s.avg, a, wscal))) return rc;
   a.profile = host ? s.profile : profile;
@@ -1164,8 +1211,8 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   for (int64_t c0 = 0; c0 < n; c0 += pass) {
     const int64_t cn = n - c0 < pass ? n - c0 : pass;
     pfe::PfdArgs b;
-    if (derive && (rc = pfd_avg_pass(h, fn, a, x32, be, q, c0, cn, s.avg.csum, wscal))) return rc;
-    if ((rc = pfd_pass(h, fn, a, x32, be, q, s.in.psum, c0, cn, b))) return rc;
+    if (derive && (rc = pfd_avg_pass(h, fn, a, x32, be, q, c0, cn, s.avg.csum, wscal, km))) return rc;
+    if ((rc = pfd_pass(h, fn, a, x32, be, q, s.in.psum, c0, cn, b, km))) return rc;
     if (a.profile) b.profile = a.profile + c0 * a.L;
     if (a.chis) b.chis = a.chis + c0 * PFE_PFD_NDM;
     if (a.lyon8) b.lyon8 = a.lyon8 + c0 * 8;
@@ -1190,44 +1237,58 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   return call_end(h);
 }
 
-// pfe_pfd_avgprof (xd) / pfe_pfd_avgprof_f32 (xf): the other cube is null
+// pfe_pfd_avgprof (xd) / pfe_pfd_avgprof_f32 (xf): the other cube is null; their _kill forms
+// (fn: the name the texts go under; kill: the caller's masks, or null)
 static int pfd_avgprof_call(pfe_handle* h, const double* xd, const float* xf, bool f32, int npart,
                             int nsub, int proflen, int64_t n, double* out, int64_t out_stride,
-                            uint32_t flags) {
+                            uint32_t flags, const char* fn = "pfd_avgprof",
+                            const pfe_pfd_kill* kill = nullptr) {
   if (!h) return PFE_EINVAL;
   h->err.clear();
-  if ((f32 ? !xf : !xd) || !out) return set_err(h, PFE_EINVAL, "pfd_avgprof: null argument");
-  if (n < 0) return set_err(h, PFE_EINVAL, "pfd_avgprof: n < 0");
+  if ((f32 ? !xf : !xd) || !out) return set_err(h, PFE_EINVAL, "%s: null argument", fn);
+  if (n < 0) return set_err(h, PFE_EINVAL, "%s: n < 0", fn);
   if (npart < 1 || nsub < 1 || proflen < 2)
-    return set_err(h, PFE_EINVAL, "pfd_avgprof: shape %dx%dx%d", npart, nsub, proflen);
-  if (out_stride < 1) return set_err(h, PFE_EINVAL, "pfd_avgprof: out_stride < 1");
+    return set_err(h, PFE_EINVAL, "%s: shape %dx%dx%d", fn, npart, nsub, proflen);
+  if (out_stride < 1) return set_err(h, PFE_EINVAL, "%s: out_stride < 1", fn);
   if (f32 && ((uintptr_t)xf & 3))
-    return set_err(h, PFE_EINVAL, "pfd_avgprof: profs not 4-byte aligned");
+    return set_err(h, PFE_EINVAL, "%s: profs not 4-byte aligned", fn);
   const bool be = flags & PFE_FLAG_PFD_BSWAP;
   if (f32 && be)
-    return set_err(h, PFE_EINVAL, "pfd_avgprof: PFE_FLAG_PFD_BSWAP is for the f64 call (8-byte values)");
+    return set_err(h, PFE_EINVAL, "%s: PFE_FLAG_PFD_BSWAP is for the f64 call (8-byte values)", fn);
   if (n == 0) return PFE_OK;
   int rc = call_begin(h);
   if (rc) return rc;
   const int64_t E = (int64_t)npart * nsub * proflen;
   const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
+  const bool killed = pfd_killed(kill);
+  pfe::PfdKillSrc kmask;
+  if (killed) kmask = pfd_kill_src(kill);
   pfe::PfdAvgStage s;
-  rc = lay_out(h, s, [&](pfe::Arena& A) { return pfe::pfd_avgprof_layout(A, E, n, host, f32); });
+  rc = lay_out(h, s, [&](pfe::Arena& A) {
+    return pfe::pfd_avgprof_layout(A, E, n, host, f32, pfe::PFD_I16_NONE, 0, kmask.mask(), npart, nsub);
+  });
   if (rc) return rc;
   if (host) {
     if ((rc = f32 ? stage_in(h, s.profs32, xf, (size_t)n * E) : stage_in(h, s.profs, xd, (size_t)n * E)))
       return rc;
     xf = s.profs32;
     xd = s.profs;
+    if (killed && (rc = stage_kill(h, kmask, s.kparts, s.ksubs, n, npart, nsub))) return rc;
   }
   double* dout = host ? s.out : out;
   const int64_t dstride = host ? 1 : out_stride;
   const hipError_t e =
-      f32  ? pfe::launch_pfd_avgprof_f32(xf, E, proflen, n, s.csum, dout, dstride, h->stream)
+      killed ? pfe::launch_pfd_avgprof_kill(f32 ? (const void*)xf : (const void*)xd,
+                                            f32  ? pfe::PFD_KILL_F32
+                                            : be ? pfe::PFD_KILL_BE64
+                                                 : pfe::PFD_KILL_F64,
+                                            kmask, npart, nsub, proflen, n, s.csum, dout, dstride,
+                                            h->stream)
+      : f32 ? pfe::launch_pfd_avgprof_f32(xf, E, proflen, n, s.csum, dout, dstride, h->stream)
       : be ? pfe::launch_pfd_avgprof_be64(xd, E, proflen, n, s.csum, dout, dstride, h->stream)
            : pfe::launch_pfd_avgprof(xd, E, proflen, n, s.csum, dout, dstride, h->stream);
   if (e != hipSuccess)
-    return set_err(h, PFE_EDEVICE, "pfd_avgprof launch: %s", hipGetErrorString(e));
+    return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
   if (host) {
     // the n values as one block, then to their places among the caller's doubles
     std::vector<double> dense;
@@ -1253,6 +1314,20 @@ int pfe_pfd_avgprof_f32(pfe_handle* h, const float* profs, int32_t npart, int32_
                         int32_t proflen, int64_t n, double* out, int64_t out_stride,
                         uint32_t flags) {
   return pfd_avgprof_call(h, nullptr, profs, true, npart, nsub, proflen, n, out, out_stride, flags);
+}
+
+int pfe_pfd_avgprof_kill(pfe_handle* h, const double* profs, int32_t npart, int32_t nsub,
+                         int32_t proflen, int64_t n, const pfe_pfd_kill* kill, double* out,
+                         int64_t out_stride, uint32_t flags) {
+  return pfd_avgprof_call(h, profs, nullptr, false, npart, nsub, proflen, n, out, out_stride, flags,
+                          "pfd_avgprof_kill", kill);
+}
+
+int pfe_pfd_avgprof_kill_f32(pfe_handle* h, const float* profs, int32_t npart, int32_t nsub,
+                             int32_t proflen, int64_t n, const pfe_pfd_kill* kill, double* out,
+                             int64_t out_stride, uint32_t flags) {
+  return pfd_avgprof_call(h, nullptr, profs, true, npart, nsub, proflen, n, out, out_stride, flags,
+                          "pfd_avgprof_kill", kill);
 }
 
 // pfe_pfd_avgprof_i16: the four arrays, the strides and the shape of `in` only
@@ -1337,6 +1412,21 @@ int pfe_pfd_dmprof_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* profile,
   return pfd_dmprof_call(h, v.view, true, v.x32, profile, chis, lyon8, status, flags);
 }
 
+int pfe_pfd_dmprof_kill(pfe_handle* h, const pfe_pfd_in* in, const pfe_pfd_kill* kill,
+                        double* profile, float* chis, double* lyon8, uint32_t* status,
+                        uint32_t flags) {
+  return pfd_dmprof_call(h, in, false, nullptr, profile, chis, lyon8, status, flags, nullptr, nullptr,
+                         true, kill);
+}
+
+int pfe_pfd_dmprof_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe_pfd_kill* kill,
+                            double* profile, float* chis, double* lyon8, uint32_t* status,
+                            uint32_t flags) {
+  const PfdF32View v(in);
+  return pfd_dmprof_call(h, v.view, true, v.x32, profile, chis, lyon8, status, flags, nullptr,
+                         nullptr, true, kill);
+}
+
 }  // extern "C"
 
 // pfe_pfd_bates22 (groups = PFD_G_ALL: out n x 22) and the PFD group calls (one group: its k
@@ -1345,7 +1435,7 @@ int pfe_pfd_dmprof_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* profile,
 static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const float* x32,
                            double* out, uint32_t* status, uint32_t flags, const char* fn,
                            unsigned groups, int c0, int k, const pfe_pfd_i16_in* i16 = nullptr,
-                           pfe::PfdI16Src* q = nullptr) {
+                           pfe::PfdI16Src* q = nullptr, const pfe_pfd_kill* kill = nullptr) {
   int64_t n;
   int rc = call_check(h, fn, in, out && status, n);
   if (rc || n == 0) return rc;
@@ -1360,7 +1450,11 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   if ((rc = call_begin(h))) return rc;
   // folds per pass: all of them, or what the part sums of a float32, byte-reversed or int16
   // cube allow
-  const bool be = !q && (flags & PFE_FLAG_PFD_BSWAP), sums = f32 || be || q;
+  const bool be = !q && (flags & PFE_FLAG_PFD_BSWAP), killed = pfd_killed(kill);
+  const bool sums = f32 || be || q || killed;
+  pfe::PfdKillSrc kmask;
+  if (killed) kmask = pfd_kill_src(kill);
+  const pfe::PfdKillSrc* km = killed ? &kmask : nullptr;
   const int ki = !q ? pfe::PFD_I16_NONE : q->wts ? pfe::PFD_I16_WEIGHTS : pfe::PFD_I16_PLAIN;
   const int64_t pass =
       sums ? pfe::pfd_f32_chunk(in->nsub, in->proflen, n, h->opt.pfd_f32_chunk) : n;
@@ -1378,7 +1472,8 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   auto walk = [&](int64_t cn) {
     return [&, cn](pfe::Arena& A) {
       return pfe::pfd_scores_layout(A, *in, host, groups, k, plan(cn).bytes(), cus, h->opt,
-                                    sums ? pass : 0, cn, derive, be, ki);
+                                    sums ? pass : 0, cn, derive, be || (killed && !f32), ki,
+                                    kmask.mask());
     };
   };
   if (n % pass) {  // a shorter last pass: its layout fits as well
@@ -1389,6 +1484,8 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   pfe::PfdScoresStage s;
   rc = lay_out(h, s, walk(pass));
   if (rc || (host && (rc = stage_pfd(h, in, x32, q, s.in, a)))) return rc;
+  if (host && killed && (rc = stage_kill(h, kmask, s.in.kparts, s.in.ksubs, n, in->npart, in->nsub)))
+    return rc;
   double* wscal = nullptr;
   if (derive && (rc = pfd_avg_begin(h, in, host ? s.in.scal : nullptr, s.avg, a, wscal))) return rc;
   double* dout = host ? s.out : out;
@@ -1400,8 +1497,8 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
       s = walk(cn)(place);
     }
     pfe::PfdArgs b;
-    if (derive && (rc = pfd_avg_pass(h, fn, a, x32, be, q, f0, cn, s.avg.csum, wscal))) return rc;
-    if ((rc = pfd_pass(h, fn, a, x32, be, q, s.in.psum, f0, cn, b))) return rc;
+    if (derive && (rc = pfd_avg_pass(h, fn, a, x32, be, q, f0, cn, s.avg.csum, wscal, km))) return rc;
+    if ((rc = pfd_pass(h, fn, a, x32, be, q, s.in.psum, f0, cn, b, km))) return rc;
     // a group call scores into a 22-column scratch of its own
     double* d22 = all ? dout + f0 * 22 : s.d22;
     if (useg) {
@@ -1444,6 +1541,21 @@ static int pfd_scores_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, 
                           uint32_t flags, const PfdScores& c) {
   const PfdF32View v(in);
   return pfd_scores_call(h, v.view, true, v.x32, out, status, flags, c.fn, c.groups, c.c0, c.k);
+}
+
+// the _kill forms: the texts under the _kill name, the masks beside `in`
+static int pfd_scores_kill(pfe_handle* h, const pfe_pfd_in* in, const pfe_pfd_kill* kill, double* out,
+                           uint32_t* status, uint32_t flags, const PfdScores& c) {
+  const std::string fn = std::string(c.fn) + "_kill";
+  return pfd_scores_call(h, in, false, nullptr, out, status, flags, fn.c_str(), c.groups, c.c0, c.k,
+                         nullptr, nullptr, kill);
+}
+static int pfd_scores_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe_pfd_kill* kill,
+                               double* out, uint32_t* status, uint32_t flags, const PfdScores& c) {
+  const PfdF32View v(in);
+  const std::string fn = std::string(c.fn) + "_kill";
+  return pfd_scores_call(h, v.view, true, v.x32, out, status, flags, fn.c_str(), c.groups, c.c0,
+                         c.k, nullptr, nullptr, kill);
 }
 
 static int pfd_scores_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, uint32_t* status,
@@ -1505,6 +1617,46 @@ int pfe_pfd_dmfit4_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uin
 int pfe_pfd_subband3_f32(pfe_handle* h, const pfe_pfd_f32_in* in, double* out, uint32_t* status,
                          uint32_t flags) {
   return pfd_scores_f32(h, in, out, status, flags, PFD_SUBBAND3);
+}
+
+int pfe_pfd_bates22_kill(pfe_handle* h, const pfe_pfd_in* in, const pfe_pfd_kill* kill, double* out,
+                        uint32_t* status, uint32_t flags) {
+  return pfd_scores_kill(h, in, kill, out, status, flags, PFD_BATES22);
+}
+
+int pfe_pfd_params4_kill(pfe_handle* h, const pfe_pfd_in* in, const pfe_pfd_kill* kill, double* out,
+                        uint32_t* status, uint32_t flags) {
+  return pfd_scores_kill(h, in, kill, out, status, flags, PFD_PARAMS4);
+}
+
+int pfe_pfd_dmfit4_kill(pfe_handle* h, const pfe_pfd_in* in, const pfe_pfd_kill* kill, double* out,
+                       uint32_t* status, uint32_t flags) {
+  return pfd_scores_kill(h, in, kill, out, status, flags, PFD_DMFIT4);
+}
+
+int pfe_pfd_subband3_kill(pfe_handle* h, const pfe_pfd_in* in, const pfe_pfd_kill* kill, double* out,
+                         uint32_t* status, uint32_t flags) {
+  return pfd_scores_kill(h, in, kill, out, status, flags, PFD_SUBBAND3);
+}
+
+int pfe_pfd_bates22_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe_pfd_kill* kill,
+                            double* out, uint32_t* status, uint32_t flags) {
+  return pfd_scores_kill_f32(h, in, kill, out, status, flags, PFD_BATES22);
+}
+
+int pfe_pfd_params4_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe_pfd_kill* kill,
+                            double* out, uint32_t* status, uint32_t flags) {
+  return pfd_scores_kill_f32(h, in, kill, out, status, flags, PFD_PARAMS4);
+}
+
+int pfe_pfd_dmfit4_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe_pfd_kill* kill,
+                           double* out, uint32_t* status, uint32_t flags) {
+  return pfd_scores_kill_f32(h, in, kill, out, status, flags, PFD_DMFIT4);
+}
+
+int pfe_pfd_subband3_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe_pfd_kill* kill,
+                             double* out, uint32_t* status, uint32_t flags) {
+  return pfd_scores_kill_f32(h, in, kill, out, status, flags, PFD_SUBBAND3);
 }
 
 }  // extern "C"

@@ -420,6 +420,39 @@ inline PfdI16Src pfd_i16_src(const pfe_pfd_i16_in& in, bool bswap) {
 hipError_t launch_pfd_partsum_i16(const PfdI16Src& x, double* s, int npart, int nsub, int L,
                                   int64_t n, hipStream_t st);
 
+// ---- kill masks: the pfe_pfd_*_kill calls (pfd_kill.hip) ---------------------------------
+// A masked call, f64 included, is the float32 call with a selection at the load: passes of
+// pfd_f32_chunk folds (PFE_OPT_PFD_F32_CHUNK governs this path too), k_pfd_partsum_kill summing
+// the selected values of the pass's folds -- +0.0 where the part or the sub-band of the value is
+// killed -- into psum, the f64 kernels on psum with npart = 1.  The scratch of a masked call
+// (kill != 0 in the layouts below: PFD_KILL_PARTS | PFD_KILL_SUBS, each mask that is given), in
+// order:
+//   host pointers: [profs (8 bytes a value; be64 = true in the layouts, reversed or not) or
+//                  profs32][subfreqs][scal][kill_parts: n x npart bytes][kill_subs: n x nsub
+//                  bytes][the outputs the call stages][status]
+//   then, host pointers or device:
+//                  [psum: chunk x nsub x proflen doubles]
+//                  [PFE_FLAG_PFD_AVGPROF: avg_csum of chunk folds (and avg_scal, device pointers)]
+//                  [the scratch of the f64 call on the folds of one pass]
+enum PfdKillMask { PFD_KILL_NONE = 0, PFD_KILL_PARTS = 1, PFD_KILL_SUBS = 2 };
+enum PfdKillElem { PFD_KILL_F64 = 0, PFD_KILL_BE64 = 1, PFD_KILL_F32 = 2 };
+// the masks of a launch on the device: parts n x npart, subs n x nsub bytes, non-zero = killed,
+// either null (none killed)
+struct PfdKillSrc {
+  const uint8_t *parts = nullptr, *subs = nullptr;
+  PfdKillSrc from(int64_t c0, int npart, int nsub) const {  // folds c0 ..
+    PfdKillSrc r;
+    r.parts = parts ? parts + c0 * npart : nullptr;
+    r.subs = subs ? subs + c0 * nsub : nullptr;
+    return r;
+  }
+  int mask() const { return (parts ? PFD_KILL_PARTS : 0) | (subs ? PFD_KILL_SUBS : 0); }
+};
+// s[c][e] = v(c,0,e) + ... + v(c,npart-1,e), v the value of x (elem: doubles, byte-reversed
+// doubles, floats) or +0.0 where k kills its part or its sub-band; e over nsub x L, c over n folds
+hipError_t launch_pfd_partsum_kill(const void* x, int elem, const PfdKillSrc& k, double* s,
+                                   int npart, int nsub, int L, int64_t n, hipStream_t st);
+
 // ---- a fold's average: pfe_pfd_avgprof and PFE_FLAG_PFD_AVGPROF (pfd_avgprof.hip) --------
 // numpy's (profs / proflen).sum() of each fold: k_pfd_avgprof sums every chunk of
 // PFD_AVG_CHUNK values (numpy's reduction buffer) of a fold's E = npart x nsub x proflen into
@@ -438,18 +471,26 @@ hipError_t launch_pfd_avgprof_be64(const double* x, int64_t E, int L, int64_t n,
 // in the order (p, s, b)
 hipError_t launch_pfd_avgprof_i16(const PfdI16Src& x, int npart, int nsub, int L, int64_t n,
                                   double* csum, double* out, int64_t stride, hipStream_t st);
+// a masked cube (x and elem as for launch_pfd_partsum_kill): each value selected where it is
+// loaded, +0.0 where killed, the n folds' E = npart x nsub x L values in the order (p, s, b)
+hipError_t launch_pfd_avgprof_kill(const void* x, int elem, const PfdKillSrc& k, int npart, int nsub,
+                                   int L, int64_t n, double* csum, double* out, int64_t stride,
+                                   hipStream_t st);
 
 // pfe_pfd_avgprof / pfe_pfd_avgprof_f32: a host-pointer call stages the cube (as the values it
-// holds) and its n results; the chunk sums follow
+// holds) and its n results; the chunk sums follow.  A masked call (kill: PfdKillMask bits, with
+// the fold's npart and nsub) stages its masks directly behind the cube, parts then subs
 struct PfdAvgStage {
   double* profs = nullptr;
   float* profs32 = nullptr;
   int16_t* data16 = nullptr;  // pfe_pfd_avgprof_i16: the cube and its parameters (ES = npart x nsub)
   float *scl16 = nullptr, *offs16 = nullptr, *wts16 = nullptr;
+  uint8_t *kparts = nullptr, *ksubs = nullptr;
   double *out = nullptr, *csum = nullptr;
 };
 inline PfdAvgStage pfd_avgprof_layout(Arena& A, int64_t E, int64_t n, bool host, bool f32,
-                                      int i16 = PFD_I16_NONE, int64_t ES = 0) {
+                                      int i16 = PFD_I16_NONE, int64_t ES = 0, int kill = 0,
+                                      int npart = 0, int nsub = 0) {
   PfdAvgStage s;
   if (host) {
     if (i16) {
@@ -461,6 +502,8 @@ inline PfdAvgStage pfd_avgprof_layout(Arena& A, int64_t E, int64_t n, bool host,
       s.profs32 = A.take<float>((size_t)n * E, "profs32");
     else
       s.profs = A.take<double>((size_t)n * E, "profs");
+    if (kill & PFD_KILL_PARTS) s.kparts = A.take<uint8_t>((size_t)n * npart, "kill_parts");
+    if (kill & PFD_KILL_SUBS) s.ksubs = A.take<uint8_t>((size_t)n * nsub, "kill_subs");
     s.out = A.take<double>((size_t)n, "out");
   }
   s.csum = A.take<double>((size_t)n * pfd_avg_chunks(E), "avg_csum");
@@ -484,16 +527,18 @@ inline PfdAvgWork pfd_avg_work_layout(Arena& A, const pfe_pfd_in& in, bool host,
 
 // the three inputs every PFD call stages.  A float32 call (f32_chunk > 0: its folds per pass)
 // stages the cube as the floats it is (profs32, no profs), and -- host pointers or device --
-// takes psum behind its staged arrays
+// takes psum behind its staged arrays.  A masked call (kill: PfdKillMask bits) stages its masks
+// directly behind scal, parts then subs, each only when given
 struct PfdInputs {
   double *profs = nullptr, *subfreqs = nullptr, *scal = nullptr;
   float* profs32 = nullptr;
   int16_t* data16 = nullptr;  // an int16 call: the cube and its parameters
   float *scl16 = nullptr, *offs16 = nullptr, *wts16 = nullptr;
+  uint8_t *kparts = nullptr, *ksubs = nullptr;
   double* psum = nullptr;
 };
 inline PfdInputs pfd_inputs_layout(Arena& A, const pfe_pfd_in& in, bool f32 = false,
-                                   int i16 = PFD_I16_NONE) {
+                                   int i16 = PFD_I16_NONE, int kill = 0) {
   PfdInputs s;
   const size_t n = (size_t)in.n, cube = n * in.npart * in.nsub * in.proflen;
   if (i16) {
@@ -508,6 +553,8 @@ inline PfdInputs pfd_inputs_layout(Arena& A, const pfe_pfd_in& in, bool f32 = fa
     s.profs = A.take<double>(cube, "profs");
   s.subfreqs = A.take<double>(n * in.nsub, "subfreqs");
   s.scal = A.take<double>(n * PFE_PFD_NSCAL, "scal");
+  if (kill & PFD_KILL_PARTS) s.kparts = A.take<uint8_t>(n * in.npart, "kill_parts");
+  if (kill & PFD_KILL_SUBS) s.ksubs = A.take<uint8_t>(n * in.nsub, "kill_subs");
   return s;
 }
 inline double* pfd_psum_layout(Arena& A, const pfe_pfd_in& in, int64_t f32_chunk) {
@@ -520,7 +567,8 @@ inline double* pfd_psum_layout(Arena& A, const pfe_pfd_in& in, int64_t f32_chunk
 // then what one pass needs.  avgprof (PFE_FLAG_PFD_AVGPROF): pfd_avg_work_layout behind psum.
 // be64 (PFE_FLAG_PFD_BSWAP, with f32_chunk > 0): the same passes on the cube staged as the
 // 8-byte words it holds (profs).  i16 (an int16 call, with f32_chunk > 0; be64 false, whatever
-// the flag): the same passes on the cube staged as int16 with its parameters
+// the flag): the same passes on the cube staged as int16 with its parameters.  kill (a masked
+// call, with f32_chunk > 0; be64 true for an f64 cube, reversed or not): the masks behind scal
 struct PfdDmprofStage {
   PfdInputs in;
   PfdAvgWork avg;
@@ -533,11 +581,12 @@ struct PfdDmprofStage {
 inline PfdDmprofStage pfd_dmprof_layout(Arena& A, const pfe_pfd_in& in, bool host, bool profile,
                                         bool chis, bool lyon8, size_t ws_bytes,
                                         int64_t f32_chunk = 0, bool avgprof = false,
-                                        bool be64 = false, int i16 = PFD_I16_NONE) {
+                                        bool be64 = false, int i16 = PFD_I16_NONE,
+                                        int kill = 0) {
   PfdDmprofStage s;
   const size_t n = (size_t)in.n;
   if (host) {
-    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64, i16);
+    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64, i16, kill);
     if (profile) s.profile = A.take<double>(n * in.proflen, "profile");
     if (chis) s.chis = A.take<float>(n * PFE_PFD_NDM, "chis");
     if (lyon8) s.lyon8 = A.take<double>(n * 8, "lyon8");
@@ -558,7 +607,8 @@ inline PfdDmprofStage pfd_dmprof_layout(Arena& A, const pfe_pfd_in& in, bool hos
 // (PFE_FLAG_PFD_AVGPROF on a call that reads the average): pfd_avg_work_layout behind psum,
 // sized by f32_chunk, so it stays put as well.  be64 (PFE_FLAG_PFD_BSWAP, with f32_chunk > 0):
 // the float32 layout with the cube staged as the 8-byte words it holds (profs).  i16 (an int16
-// call, with f32_chunk > 0; be64 false): the float32 layout with the int16 cube and its parameters
+// call, with f32_chunk > 0; be64 false): the float32 layout with the int16 cube and its parameters.
+// kill (a masked call, with f32_chunk > 0; be64 true for an f64 cube): the masks behind scal
 struct PfdScoresStage {
   PfdInputs in;
   PfdAvgWork avg;
@@ -571,12 +621,13 @@ inline PfdScoresStage pfd_scores_layout(Arena& A, const pfe_pfd_in& in, bool hos
                                         unsigned groups, int k, size_t g_bytes, int cus,
                                         const Options& o, int64_t f32_chunk = 0,
                                         int64_t pass = 0, bool avgprof = false,
-                                        bool be64 = false, int i16 = PFD_I16_NONE) {
+                                        bool be64 = false, int i16 = PFD_I16_NONE,
+                                        int kill = 0) {
   PfdScoresStage s;
   const size_t n = (size_t)in.n;
   const int64_t wn = f32_chunk > 0 ? pass : in.n;
   if (host) {
-    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64, i16);
+    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64, i16, kill);
     s.out = A.take<double>(n * k, "out");
     s.status = A.take<uint32_t>(n, "status");
   }

@@ -104,6 +104,44 @@ struct i16_cube {
   unsigned E1, L;
 };
 
+// A value of a masked cube (the _kill calls, pfd_kill.hip) as loaded with the kill bit of its
+// (part, sub-band): widened to double through the selection, +0.0 where killed -- replaced,
+// never multiplied, so what a killed row holds reaches no sum.  T: double, be64 or float
+template <typename T>
+struct kill_elem {
+  T v;
+  bool dead;
+  __device__ __forceinline__ explicit operator double() const { return dead ? 0.0 : (double)v; }
+};
+// Where a pointer into the cube stands, for one fold of a masked cube: values [at, ...) of the
+// fold in the order (p, s, b), at = part p0 and element r of that part, as for i16_cursor
+template <typename T>
+struct kill_cursor {
+  const T* x;                   // the fold's part p0
+  const uint8_t *parts, *subs;  // the fold's masks, parts from p0 on; either null
+  unsigned E1, L, r;
+  __device__ __forceinline__ kill_cursor operator+(int k) const {
+    kill_cursor c = *this;
+    c.r += (unsigned)k;
+    return c;
+  }
+  __device__ __forceinline__ kill_elem<T> operator[](int k) const {
+    const unsigned j = r + (unsigned)k, p = j / E1, e = j - p * E1;
+    kill_elem<T> v;
+    v.v = x[j];
+    v.dead = (parts && parts[p] != 0) || (subs && subs[e / L] != 0);
+    return v;
+  }
+};
+// the masked cube of a launch: dense, n x NP x E1 values, parts n x NP and subs n x nsub bytes
+template <typename T>
+struct kill_cube {
+  const T* x;
+  PfdKillSrc k;
+  int NP, nsub;
+  unsigned E1, L;
+};
+
 // the values of `fold` from its e0-th on: a pointer, or a cursor
 template <typename T>
 __device__ __forceinline__ const T* avg_at(const T* X, int64_t fold, int64_t E, int64_t e0) {
@@ -120,6 +158,20 @@ __device__ __forceinline__ i16_cursor<BS, WT> avg_at(const i16_cube<BS, WT>& X, 
   c.wts = WT ? X.x.wts + fold * X.x.pfs + p0 * X.x.pps : nullptr;
   c.dps = X.x.dps;
   c.pps = X.x.pps;
+  c.E1 = X.E1;
+  c.L = X.L;
+  c.r = (unsigned)(e0 - p0 * X.E1);
+  return c;
+}
+
+template <typename T>
+__device__ __forceinline__ kill_cursor<T> avg_at(const kill_cube<T>& X, int64_t fold, int64_t E,
+                                                 int64_t e0) {
+  const int64_t p0 = e0 / X.E1;
+  kill_cursor<T> c;
+  c.x = X.x + fold * E + p0 * X.E1;
+  c.parts = X.k.parts ? X.k.parts + fold * X.NP + p0 : nullptr;
+  c.subs = X.k.subs ? X.k.subs + fold * X.nsub : nullptr;
   c.E1 = X.E1;
   c.L = X.L;
   c.r = (unsigned)(e0 - p0 * X.E1);
@@ -316,6 +368,25 @@ hipError_t launch_pfd_avgprof_i16(const PfdI16Src& x, int npart, int nsub, int L
   if (E1 < 1 || E1 > 0x7fffffff - PFD_AVG_CHUNK) return hipErrorInvalidValue;  // i16_cursor's 32 bits
   return x.bswap ? launch_avgprof_i16<true>(x, (unsigned)E1, E, L, n, csum, out, stride, st)
                  : launch_avgprof_i16<false>(x, (unsigned)E1, E, L, n, csum, out, stride, st);
+}
+template <typename T>
+static hipError_t launch_avgprof_kill(const void* x, const PfdKillSrc& k, int npart, int nsub, int L,
+                                      int64_t n, double* csum, double* out, int64_t stride,
+                                      hipStream_t st) {
+  const int64_t E1 = (int64_t)nsub * L, E = E1 * npart;
+  if (E1 < 1 || E1 > 0x7fffffff - PFD_AVG_CHUNK) return hipErrorInvalidValue;  // kill_cursor's 32 bits
+  return launch_avgprof(kill_cube<T>{static_cast<const T*>(x), k, npart, nsub, (unsigned)E1, (unsigned)L},
+                        E, L, n, csum, out, stride, st);
+}
+hipError_t launch_pfd_avgprof_kill(const void* x, int elem, const PfdKillSrc& k, int npart, int nsub,
+                                   int L, int64_t n, double* csum, double* out, int64_t stride,
+                                   hipStream_t st) {
+  switch (elem) {
+    case PFD_KILL_F64: return launch_avgprof_kill<double>(x, k, npart, nsub, L, n, csum, out, stride, st);
+    case PFD_KILL_BE64: return launch_avgprof_kill<be64>(x, k, npart, nsub, L, n, csum, out, stride, st);
+    case PFD_KILL_F32: return launch_avgprof_kill<float>(x, k, npart, nsub, L, n, csum, out, stride, st);
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace pfe

@@ -113,7 +113,65 @@ def read(path: str, avgprof: bool = True) -> PFDData:
         fold_p1=vals["fold"][1], orb=orb, dms=dms, periods=periods, pdots=pdots, profs=profs,
         stats=stats, binspersec=binspersec, chanpersub=chanpersub, subdeltafreq=subdeltafreq,
         losubfreq=losubfreq, subfreqs=subfreqs, avgprof=(profs / proflen).sum() if avgprof else None,
-        varprof=varprof)
+        varprof=varprof, killed_subbands=[], killed_intervals=[])
+
+
+def varprof(prof_var, kill_parts=None, kill_subs=None):
+    """calc_varprof (PFDFile.py:314-326) for a batch: prof_var (..., npart, nsub), the
+    foldstats' column 5 -> (...,) the sequential sum in (part, sub) order from 0.0, the rows of
+    killed parts (..., npart) and sub-bands (..., nsub) skipped; a 1-D mask is for every fold.
+    Skipping a term and adding +0.0 in its place give the same bits (x + 0.0 == x, and the sum
+    starts from +0.0), so this is np.add.accumulate over np.where(kill, 0.0, v)."""
+    v = np.asarray(prof_var, dtype=np.float64)
+    if v.ndim < 2:
+        raise ValueError("varprof: prof_var must be (..., npart, nsub)")
+    kill = np.zeros(v.shape, dtype=bool)
+    if kill_parts is not None:
+        kill |= np.asarray(kill_parts).astype(bool)[..., :, None]
+    if kill_subs is not None:
+        kill |= np.asarray(kill_subs).astype(bool)[..., None, :]
+    z = np.where(kill, 0.0, v).reshape(v.shape[:-2] + (-1,))
+    if z.shape[-1] == 0:
+        return np.zeros(v.shape[:-2])
+    # accumulate is sequential (no pairwise blocks); 0.0 + z[0] is z[0] bit for bit but for
+    # z[0] = -0.0, where the loop from 0.0 gives +0.0
+    return np.add.accumulate(z, axis=-1)[..., -1] + 0.0
+
+
+def parse_kill_list(text):
+    """show_pfd's -killsubs / -killparts syntax: '0,3:5' -> [0, 3, 4, 5] (ranges inclusive)."""
+    out = []
+    for tok in str(text).split(","):
+        tok = tok.strip()
+        if not tok:
+            continue
+        lo, sep, hi = tok.partition(":")
+        try:
+            a = int(lo)
+            b = int(hi) if sep else a
+        except ValueError:
+            raise ValueError(f"bad kill list {text!r}: {tok!r} is neither N nor LO:HI") from None
+        if a < 0 or b < a:
+            raise ValueError(f"bad kill list {text!r}: {tok!r} must be 0 <= LO <= HI")
+        out.extend(range(a, b + 1))
+    return out
+
+
+def kill_masks(datas):
+    """The killed_intervals / killed_subbands lists of PFDData of one shape as the uint8 masks
+    of the PFD calls -> (kill_parts (n,npart), kill_subs (n,nsub)), or (None, None) when no
+    fold has anything killed."""
+    lists = [(getattr(d, "killed_intervals", None) or [], getattr(d, "killed_subbands", None) or [])
+             for d in datas]
+    if not any(kp or ks for kp, ks in lists):
+        return None, None
+    d0 = datas[0]
+    parts = np.zeros((len(datas), d0.npart), dtype=np.uint8)
+    subs = np.zeros((len(datas), d0.nsub), dtype=np.uint8)
+    for i, (kp, ks) in enumerate(lists):
+        parts[i, list(kp)] = 1
+        subs[i, list(ks)] = 1
+    return parts, subs
 
 
 def write(path: str, *, profs, stats=None, dms, bestdm, fold_p1, bary_p1=None, lofreq=1200.0,

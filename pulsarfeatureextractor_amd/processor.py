@@ -249,20 +249,50 @@ def _read_pfd(path):
         return None, f"{type(e).__name__}: {e}"
 
 
-def _pfd_call(engine, fn, datas, **kw):
+def _kill_masks(kill, npart, nsub):
+    """The run's kill lists (kill_subbands, kill_intervals) as the 1-D masks of the PFD calls for
+    folds of one shape -> dict(kill_parts=, kill_subs=); {} when nothing is killed.  An index the
+    shape does not have is the folds' error (PfeError: they fail alone, like a refused shape)."""
+    if not kill or not (kill[0] or kill[1]):
+        return {}
+    subs, parts = kill
+    for what, idx, limit in (("sub-band", subs, nsub), ("interval", parts, npart)):
+        bad = [i for i in idx if not 0 <= i < limit]
+        if bad:
+            raise PfeError(f"IndexError: killed {what} {bad[0]} out of range: the fold has {limit}")
+    kp = np.zeros(npart, dtype=np.uint8)
+    ks = np.zeros(nsub, dtype=np.uint8)
+    kp[list(parts)] = 1
+    ks[list(subs)] = 1
+    return {"kill_parts": kp, "kill_subs": ks}
+
+
+def _pfd_call(engine, fn, datas, kill=None, **kw):
     """engine.<fn> on the packed folds.  libpfe derives every fold's average from the cube on
     the device (derive_avgprof: scal[:, 2] is not read, so folds read with avgprof=False need
     no pass over the cube here); any other engine gets scal complete, a missing average
-    filled in as PFDFile.load computes it."""
+    filled in as PFDFile.load computes it.  kill: the run's kill lists -- the folds are scored
+    with those rows killed (libpfe: the _kill calls on the cube as it is; any other engine: on a
+    zapped copy), scal[:, 3] the varprof of the rows that are left (calc_varprof)."""
     from ._native import Engine
 
+    masks = _kill_masks(kill, datas[0].npart, datas[0].nsub)
     if isinstance(engine, Engine):
         kw["derive_avgprof"] = True
+        kw.update(masks)
     else:
         for d in datas:
-            if d.avgprof is None:
+            if d.avgprof is None and not masks:
                 d.avgprof = (d.profs / d.proflen).sum()
-    return getattr(engine, fn)(*_pfd.batch_inputs(datas), **kw)
+    profs, subfreqs, scal = _pfd.batch_inputs(datas)
+    if masks:
+        scal[:, 3] = _pfd.varprof(np.stack([d.stats[:, :, 5] for d in datas]), masks["kill_parts"],
+                                  masks["kill_subs"])
+        if not isinstance(engine, Engine):
+            dead = masks["kill_parts"].astype(bool)[:, None, None] | masks["kill_subs"].astype(bool)[:, None]
+            profs = np.where(dead, 0.0, profs)
+            scal[:, 2] = [(z / z.shape[-1]).sum() for z in profs]
+    return getattr(engine, fn)(profs, subfreqs, scal, **kw)
 
 
 PFD_SLAB_BYTES = 256 << 20  # cube bytes of one pack of natively read folds (at least one fold)
@@ -278,9 +308,11 @@ class NativeFolds:
     each pack is scored by the same Engine.pfd_* methods as parsed folds, with the average
     derived and a big-endian group's byte order dealt with on the device."""
 
-    def __init__(self, batch, info, rows, slabs, threads=0, slab_bytes=PFD_SLAB_BYTES, run=None):
+    def __init__(self, batch, info, rows, slabs, threads=0, slab_bytes=PFD_SLAB_BYTES, run=None,
+                 kill=None):
         self.batch, self.info, self.rows = batch, info, np.asarray(rows, dtype=np.int64)
         self.slabs, self.threads, self.slab_bytes, self.run = slabs, threads, int(slab_bytes), run
+        self.kill = kill  # the run's (kill_subbands, kill_intervals), or None
 
     def __len__(self):
         return len(self.rows)
@@ -309,7 +341,27 @@ class NativeFolds:
                 if self.run is not None:
                     self.run.add("pack", time.perf_counter() - t0)
 
-                def call(fn, a=a, be=be, **kw):
+                # the run's kill lists, once per pack: the masks of this shape, and varprof of the
+                # rows that are left from the files' foldstats (an index the shape does not have
+                # is the pack's error, raised by every call on it)
+                masks, refused = {}, None
+                try:
+                    masks = _kill_masks(self.kill, int(npart), int(nsub))
+                except PfeError as e:
+                    refused = e
+                if masks:
+                    from ._native import PFE_PFD_F_STATS
+
+                    count = int(npart) * int(nsub) * 7
+                    stats = np.stack([self.batch.fetch(int(r), PFE_PFD_F_STATS, count)
+                                      for r in self.rows[part]]).reshape(len(part), npart, nsub, 7)
+                    a["scal"][:, 3] = _pfd.varprof(stats[..., 5], masks["kill_parts"],
+                                                   masks["kill_subs"])
+
+                def call(fn, a=a, be=be, masks=masks, refused=refused, **kw):
+                    if refused is not None:
+                        raise refused
+                    kw.update(masks)
                     t1 = time.perf_counter()
                     try:
                         return getattr(engine, fn)(a["profs"], a["subfreqs"], a["scal"],
@@ -321,9 +373,10 @@ class NativeFolds:
                 yield [int(i) for i in part], call
 
 
-def _fold_batches(datas, engine, batch):
+def _fold_batches(datas, engine, batch, kill=None):
     """(indices into datas, call) per GPU batch; call(fn, **kw) = engine.<fn> on those folds.
-    datas: parsed folds (PFDData), grouped by shape into batches of `batch`, or NativeFolds."""
+    datas: parsed folds (PFDData), grouped by shape into batches of `batch`, or NativeFolds
+    (which carry the run's kill lists themselves; kill is for parsed folds)."""
     if isinstance(datas, NativeFolds):
         yield from datas.batches(engine)
         return
@@ -334,10 +387,10 @@ def _fold_batches(datas, engine, batch):
         for s0 in range(0, len(idx), batch):
             part = idx[s0:s0 + batch]
             yield part, (lambda fn, part=part, **kw:
-                         _pfd_call(engine, fn, [datas[i] for i in part], **kw))
+                         _pfd_call(engine, fn, [datas[i] for i in part], kill, **kw))
 
 
-def score_pfd(datas, engine=None, batch: int = 1 << 14):
+def score_pfd(datas, engine=None, batch: int = 1 << 14, kill=None):
     """PFD preprocessing + Lyon features on the GPU for parsed folds (or NativeFolds):
     returns (lyon8 (n,8), profiles [n arrays], errors [n])."""
     engine = engine or get_engine()
@@ -345,7 +398,7 @@ def score_pfd(datas, engine=None, batch: int = 1 << 14):
     out = np.full((n, 8), np.nan)
     profiles = [None] * n
     err = [None] * n
-    for part, call in _fold_batches(datas, engine, batch):
+    for part, call in _fold_batches(datas, engine, batch, kill):
         try:
             r = call("pfd_dmprof", chis=False)
         except PfeError as e:  # a shape the library refuses fails its folds, not the run
@@ -361,14 +414,14 @@ def score_pfd(datas, engine=None, batch: int = 1 << 14):
     return out, profiles, err
 
 
-def score_pfd22(datas, engine=None, batch: int = 1 << 16):
+def score_pfd22(datas, engine=None, batch: int = 1 << 16, kill=None):
     """22 scores of parsed PFD folds (or NativeFolds) on the GPU (pfe_pfd_bates22,
     PFDFile.compute): returns (scores (n,22), error message or None per fold)."""
     engine = engine or get_engine()
     n = len(datas)
     out = np.full((n, 22), np.nan)
     err = [None] * n
-    for part, call in _fold_batches(datas, engine, batch):
+    for part, call in _fold_batches(datas, engine, batch, kill):
         try:
             o, st = call("pfd_bates22")
         except PfeError as e:  # a shape the library refuses fails its folds, not the run
@@ -384,14 +437,14 @@ def score_pfd22(datas, engine=None, batch: int = 1 << 16):
     return out, err
 
 
-def pfd_profile_and_curve(datas, engine=None, batch: int = 1 << 14):
+def pfd_profile_and_curve(datas, engine=None, batch: int = 1 << 14, kill=None):
     """The 0..255 profile and the float32 chi^2-vs-DM curve of parsed PFD folds (or
     NativeFolds) (PFDFile.computeProfileScores :479-492, getDMCurveData :494-520):
     -> (profiles [n arrays], curves [n float32 arrays], error or None per fold)."""
     engine = engine or get_engine()
     n = len(datas)
     profiles, curves, err = [None] * n, [None] * n, [None] * n
-    for part, call in _fold_batches(datas, engine, batch):
+    for part, call in _fold_batches(datas, engine, batch, kill):
         try:
             r = call("pfd_dmprof", lyon8=False)
         except PfeError as e:  # a shape the library refuses fails its folds, not the run
@@ -767,8 +820,12 @@ class DataProcessor:
     def __init__(self, debugFlag=False, engine=None, workers=None, log=print, batch=BATCH,
                  start=0, gpu_batch=1 << 18, metrics_path=None, gpu_depth=2, ramp=True,
                  gpus=1, devices=None, shard_engine=None, shard_slabs=None, native_pfd=True,
-                 pfd_slab_bytes=PFD_SLAB_BYTES):
+                 pfd_slab_bytes=PFD_SLAB_BYTES, kill_subbands=None, kill_intervals=None):
         self.debug = debugFlag
+        # show_pfd's -killsubs / -killparts for every fold of a PFD run: sub-bands and
+        # sub-integrations left out of every score (the pfe_pfd_*_kill calls; no copy of a cube)
+        self.kill_subbands = [int(i) for i in kill_subbands or []]
+        self.kill_intervals = [int(i) for i in kill_intervals or []]
         # .pfd files through the native reader (pfe_pfd_scan on the helper thread, pfe_pfd_pack
         # into the slot's pinned slab, pfd_slab_bytes of cube per pack) when the engine is
         # libpfe's; False: every file through pfd.read.  The same output bytes either way.
@@ -818,6 +875,9 @@ class DataProcessor:
     def _candidates(self, directory, regexes, single):
         """The run's candidate paths: a PathFeed whose walk runs beside the first batches'
         parsing for a directory, a list otherwise.  Run metrics "discover": the walk's time."""
+        if self._kill() and not (self.pfd and not self.phcx and not self.superb):
+            raise ValueError("kill_subbands / kill_intervals are for PFD runs only (the PFD entry "
+                             "points: processPFDCollectively, processPFDSeparately, dmprofPFD, labelPFD)")
         if self._shard is not None:  # a worker: its shard of the parent's discovery
             return list(self._shard[2])
         t0 = time.perf_counter()
@@ -1044,7 +1104,7 @@ class DataProcessor:
         native = [k for k, r in enumerate(rd) if r is None]
         if native:
             folds = NativeFolds(pre.pb, pre.pinfo, native, self._slab(slot), self.workers,
-                                self.pfd_slab_bytes, self._run)
+                                self.pfd_slab_bytes, self._run, self._kill())
             self._score_folds(folds, [pf[k] for k in native], mode, res, eng)
         # files read by pfd.read (all of them without native_pfd)
         good = [k for k, r in enumerate(rd) if r is not None and r[0] is not None]
@@ -1052,26 +1112,33 @@ class DataProcessor:
             if r is not None and r[0] is None:
                 res.err[pf[k]] = r[1]
         if good:
-            self._score_folds([rd[k][0] for k in good], [pf[k] for k in good], mode, res, eng)
+            self._score_folds([rd[k][0] for k in good], [pf[k] for k in good], mode, res, eng,
+                              self._kill())
+
+    def _kill(self):
+        """(kill_subbands, kill_intervals) of the run, or None when nothing is killed."""
+        if self.kill_subbands or self.kill_intervals:
+            return (self.kill_subbands, self.kill_intervals)
+        return None
 
     @staticmethod
-    def _score_folds(datas, dest, mode, res, eng):
+    def _score_folds(datas, dest, mode, res, eng, kill=None):
         """Folds `datas` (PFDData or NativeFolds) into rows `dest` of the batch's results."""
         if mode == "profile":       # PFDFile.computeProfileScores (:479-492)
-            _f, profiles, errs = score_pfd(datas, eng)
+            _f, profiles, errs = score_pfd(datas, eng, kill=kill)
             for j, i in enumerate(dest):
                 if profiles[j] is None:  # the fold's shape was refused
                     res.err[i] = errs[j]
                 else:
                     res.rows[i] = np.asarray(profiles[j], dtype=np.float64)
         elif mode == "lyon8":
-            feats, _prof, errs = score_pfd(datas, eng)
+            feats, _prof, errs = score_pfd(datas, eng, kill=kill)
             for j, i in enumerate(dest):
                 res.mat[i], res.err[i] = feats[j], errs[j]
         else:
-            sc, errs = score_pfd22(datas, eng)
+            sc, errs = score_pfd22(datas, eng, kill=kill)
             if mode == "label":
-                prof, chis, derr = pfd_profile_and_curve(datas, eng)
+                prof, chis, derr = pfd_profile_and_curve(datas, eng, kill=kill)
                 for j, i in enumerate(dest):
                     res.err[i] = errs[j] or derr[j]
                     if prof[j] is not None:
@@ -1318,7 +1385,8 @@ class DataProcessor:
         procs, pipes = [], []
         kw = {"debugFlag": self.debug, "workers": threads, "batch": self.batch,
               "gpu_batch": self.gpu_batch, "gpu_depth": self.depth, "ramp": self.ramp,
-              "native_pfd": self.native_pfd, "pfd_slab_bytes": self.pfd_slab_bytes}
+              "native_pfd": self.native_pfd, "pfd_slab_bytes": self.pfd_slab_bytes,
+              "kill_subbands": self.kill_subbands, "kill_intervals": self.kill_intervals}
         flags = {"phcx": self.phcx, "pfd": self.pfd, "superb": self.superb}
         # the workers start (interpreter, engine, GPU) while the walk is still listing; each
         # gets its shard of paths once the walk is done

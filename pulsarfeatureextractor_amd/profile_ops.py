@@ -344,6 +344,17 @@ class PFDOperations(ProfileOperations):
     def _inputs(self, data):
         return _pfd.batch_inputs([self._fold(data)])
 
+    def _kill(self, data):
+        """Keywords of the PFD calls for a fold with killed intervals or sub-bands
+        (PFDFile.kill_intervals / kill_subbands): its masks, and the average derived from the
+        zapped cube on the device.  {} for a fold with nothing killed -- unless it carries no
+        average (avgprof None: read with avgprof=False), which the device then derives."""
+        fold = self._fold(data)
+        parts, subs = _pfd.kill_masks([fold])
+        if parts is None:
+            return {"derive_avgprof": True} if getattr(fold, "avgprof", 0.0) is None else {}
+        return dict(kill_parts=parts, kill_subs=subs, derive_avgprof=True)
+
     # ---- batched forms -------------------------------------------------------------------
     def getSinusoidFittings_batch(self, profiles):
         p, f64 = _profile_rows(profiles)
@@ -353,25 +364,26 @@ class PFDOperations(ProfileOperations):
         p, f64 = _profile_rows(profiles)
         return self.engine.gauss7_f64(p) if f64 else super().getGaussianFittings_batch(p)
 
-    def getCandidateParameters_batch(self, profs, subfreqs, scal):
-        """Folds of one shape, as pfd.batch_inputs packs them -> ((n, 4), status)."""
-        return self.engine.pfd_params4(profs, subfreqs, scal)
+    def getCandidateParameters_batch(self, profs, subfreqs, scal, **kill):
+        """Folds of one shape, as pfd.batch_inputs packs them -> ((n, 4), status).  kill (this
+        and the next two): kill_parts / kill_subs / derive_avgprof as Engine.pfd_params4 takes."""
+        return self.engine.pfd_params4(profs, subfreqs, scal, **kill)
 
-    def getDMFittings_batch(self, profs, subfreqs, scal):
-        return self.engine.pfd_dmfit4(profs, subfreqs, scal)
+    def getDMFittings_batch(self, profs, subfreqs, scal, **kill):
+        return self.engine.pfd_dmfit4(profs, subfreqs, scal, **kill)
 
-    def getSubbandParameters_batch(self, profs, subfreqs, scal):
-        return self.engine.pfd_subband3(profs, subfreqs, scal)
+    def getSubbandParameters_batch(self, profs, subfreqs, scal, **kill):
+        return self.engine.pfd_subband3(profs, subfreqs, scal, **kill)
 
     # ---- per fold (the reference's signatures) -------------------------------------------
     def getCandidateParameters(self, data):
         """:93-233 -> [period (ms), snr, dm, width] as the method returns them (PFDFile applies
         filterScore(13/14) when it stores s13/s14)."""
-        out, _st = self.getCandidateParameters_batch(*self._inputs(data))
+        out, _st = self.getCandidateParameters_batch(*self._inputs(data), **self._kill(data))
         return [float(v) for v in out[0]]
 
     def _dm_curve(self, data):
-        r = self.engine.pfd_dmprof(*self._inputs(data), profile=False, lyon8=False)
+        r = self.engine.pfd_dmprof(*self._inputs(data), profile=False, lyon8=False, **self._kill(data))
         if int(r["status"][0]) & PFE_ST_PFD_DMCURVE_FAIL:  # numdms == 1: dms[0] raises
             raise Exception("DM curve extraction exception")
         return r["chis"][0]
@@ -387,7 +399,7 @@ class PFDOperations(ProfileOperations):
 
     def getDMFittings(self, data):
         """:274-393 -> (peak, |1 - Prop|, Shift, chi_theo) (s18 = filterScore(18, Shift))."""
-        out, st = self.getDMFittings_batch(*self._inputs(data))
+        out, st = self.getDMFittings_batch(*self._inputs(data), **self._kill(data))
         _raise_failed(st)
         return tuple(float(v) for v in out[0])
 
@@ -406,11 +418,11 @@ class PFDOperations(ProfileOperations):
             raise ValueError("getSubbandParameters: a profile without its fold")
         ins = self._inputs(data)
         if profile is not None:
-            own = self.engine.pfd_dmprof(*ins, chis=False, lyon8=False)["profile"][0]
+            own = self.engine.pfd_dmprof(*ins, chis=False, lyon8=False, **self._kill(data))["profile"][0]
             given = np.asarray(profile, dtype=np.float64)
             if given.shape != own.shape or not np.array_equal(given, own, equal_nan=True):
                 raise ValueError("getSubbandParameters: only the fold's own profile "
                                  "(PFDFile.getProfile()) is supported")
-        out, st = self.getSubbandParameters_batch(*ins)
+        out, st = self.getSubbandParameters_batch(*ins, **self._kill(data))
         _raise_failed(st)
         return [float(v) for v in out[0]]

@@ -147,6 +147,9 @@ int pfe_synchronize(pfe_handle* h);
  *                        PFE_FLAG_PFD_BSWAP: folds per pass, >= 0.  0 (default) = as many
  *                        folds as keep a pass's part sums (nsub x proflen doubles a fold)
  *                        within 1 GiB; a larger value is cut to that, and to n (same bits)
+ *   PFE_OPT_PFD_SCRUNCH_DIRECT  the pfe_pfd_scrunch calls: 0 (default) = folds whose rows fit the
+ *                        LDS are summed there and every other shape takes one lane per output
+ *                        bin; 1 = every shape one lane per output bin (same bits)
  * Returns PFE_EINVAL for an unknown option or an out-of-range value.
  * --------------------------------------------------------------------------------------- */
 #define PFE_OPT_SOLVER 1
@@ -162,6 +165,7 @@ int pfe_synchronize(pfe_handle* h);
 #define PFE_OPT_PFD_GLOBAL 11
 #define PFE_OPT_SUBF64_GLOBAL 12
 #define PFE_OPT_PFD_F32_CHUNK 13
+#define PFE_OPT_PFD_SCRUNCH_DIRECT 14
 #define PFE_SOLVER_POOLED 0
 #define PFE_SOLVER_BATCHED 1
 #define PFE_SOLVER_WAVE 2
@@ -700,6 +704,69 @@ int pfe_pfd_subband3_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe
 int pfe_pfd_avgprof_kill_f32(pfe_handle* h, const float* profs, int32_t npart, int32_t nsub,
                              int32_t proflen, int64_t n, const pfe_pfd_kill* kill, double* out,
                              int64_t out_stride, uint32_t flags);
+
+/* ---- scrunching a fold: channels to sub-bands, bins to fewer bins -------------------------
+ * prepfold writes 16-128 sub-bands of 64-256 bins, dedispersed at the fold DM inside each
+ * sub-band.  A fold-mode archive holds every channel (512-4096), often 512-2048 bins, and
+ * nothing inside a group of channels is dedispersed: pfe_pfd_bates22 refuses its proflen, the
+ * sub-band scores would correlate millions of pairs of noise rows.  The scrunch calls make the
+ * fold the PFD calls score out of such a cube where it lies, in one pass: every value is loaded
+ * once, as the value it is, and the result is stored once.
+ *
+ * Inputs for fold i: the cube x[i][p][c][b], npart x nchan x nbin; an optional rotation per
+ * channel rot[i][c], any int32; two factors, fscr dividing nchan and bscr dividing nbin.
+ * G = nchan / fscr, K = nbin / bscr.  Contract: out is z, n x G x K doubles, dense, with
+ *   S[c][b] = x[0][c][b] + x[1][c][b] + ... + x[npart-1][c][b]       from part 0's value (no 0.0 +)
+ *   r_c     = ((rot[i][c] % nbin) + nbin) % nbin                      rot == NULL: 0
+ *   R[c][b] = S[c][(b + r_c) % nbin]                                  a left rotation: np.roll(S[c], -r_c)
+ *   B[c][k] = R[c][k*bscr] + R[c][k*bscr+1] + ... + R[c][k*bscr+bscr-1]   from the first value
+ *   z[g][k] = B[g*fscr][k] + B[g*fscr+1][k] + ... + B[g*fscr+fscr-1][k]   from the first value
+ * each step in fp64, each sum in exactly this order.  A float32 cube is widened value by value
+ * first.  An int16 cube is decoded first, exactly as the _i16 contract above says: d * scl +
+ * offs, then * wts when given; a channel of weight 0 therefore adds +0.0.  Nothing is computed
+ * in float32 or in integers, and the inputs are never written.  A NaN is a NaN; which payload
+ * survives is unspecified.  With fscr = bscr = 1 and no rotation z is the part sums S the PFD
+ * kernels form.  No result depends on the route the shape takes (below).
+ *
+ * z is an ordinary fold of one part: pass it to the f64 PFD calls with npart = 1, nsub = G,
+ * proflen = K and PFE_FLAG_PFD_AVGPROF, so that the average is derived from it.  prepfold builds
+ * its sub-bands the same way -- channels aligned at the fold DM inside a sub-band, sub-bands left
+ * unaligned for the DM search -- with rot[c] the delay of channel c against the centre of its
+ * group, in bins.
+ *
+ * pfe_pfd_scrunch_i16 reads data, scl, offs, wts, the two strides, npart, nsub (= nchan), proflen
+ * (= nbin) and n of its struct; subfreqs and scal are ignored and may be NULL.  The alignment and
+ * stride rules are those of the _i16 calls, with the same texts under this name: strided table
+ * rows are for device pointers.  It honours PFE_FLAG_PFD_BSWAP.  The f64 and f32 forms refuse
+ * PFE_FLAG_PFD_BSWAP, and all forms refuse PFE_FLAG_PFD_AVGPROF (no call here reads scal), with
+ * PFE_EINVAL.  PFE_EINVAL, with a text naming the rule, also for: a null array; a factor below 1;
+ * a factor that does not divide its dimension; a cube that is not aligned to its values (8, 4,
+ * 2 bytes), rot not 4-byte, out not 8-byte aligned.  There is no shape limit: any npart, nchan,
+ * nbin >= 1, with 64-bit offsets throughout.  Stream behaviour and PFE_FLAG_DEVICE_PTRS are as in
+ * the PFD calls.
+ *
+ * How: rows with nbin (rounded up to a multiple of 4) + K <= 8192 doubles, 64 KB of LDS, take one
+ * block per (fold, group): slabs of up to 4096 values of consecutive channel rows are part-summed
+ * into the LDS -- 16-byte loads (8-byte for int16) when nbin is a multiple of 4 and the cube is
+ * aligned for them at every part, loads of single values otherwise -- and K lanes add their bscr
+ * rotated values of each row in order.  Longer rows, and every shape under
+ * PFE_OPT_PFD_SCRUNCH_DIRECT, take one lane per output bin, each value loaded alone at its
+ * rotated place.  Same adds, same order, same bits.
+ * Scratch: a host-pointer call stages the cube as the values it holds (an int16 cube as data,
+ * then scl, offs and, when given, wts as floats), then rot (when given), then out; nothing else.
+ * A device-pointer call takes no scratch. */
+typedef struct pfe_pfd_scrunch_how {
+  const int32_t* rot; /* n x nchan, any int32 (reduced mod nbin on the device); NULL = none */
+  int32_t fscr, bscr; /* >= 1; fscr divides nchan, bscr divides nbin */
+} pfe_pfd_scrunch_how;
+
+int pfe_pfd_scrunch(pfe_handle* h, const double* profs, int32_t npart, int32_t nchan, int32_t nbin,
+                    int64_t n, const pfe_pfd_scrunch_how* how, double* out, uint32_t flags);
+int pfe_pfd_scrunch_f32(pfe_handle* h, const float* profs, int32_t npart, int32_t nchan,
+                        int32_t nbin, int64_t n, const pfe_pfd_scrunch_how* how, double* out,
+                        uint32_t flags);
+int pfe_pfd_scrunch_i16(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_scrunch_how* how,
+                        double* out, uint32_t flags);
 
 /* ---- float32 candidates: the float-array calls on arrays of floats ----------------------
  * A candidate that never was a .pfd or .phcx file -- a float32 tensor from a GPU folder or a

@@ -86,6 +86,9 @@ EXPORTED_SYMBOLS = (
     "pfe_pfd_dmfit4_kill_f32",
     "pfe_pfd_subband3_kill_f32",
     "pfe_pfd_avgprof_kill_f32",
+    "pfe_pfd_scrunch",
+    "pfe_pfd_scrunch_f32",
+    "pfe_pfd_scrunch_i16",
 )
 PFE_FLAG_PFD_AVGPROF = 0x2  # PFD calls: derive scal[:, PFE_PFD_AVGPROF] from the cube
 PFE_FLAG_PFD_BSWAP = 0x4    # f64 and int16 PFD calls: the cube (int16: and scl, offs, wts) byte-reversed
@@ -140,6 +143,7 @@ OPTIONS = {
     "subf64_global": 12,  # float sub-bands: 0 shapes that fit stay in LDS (default), 1 all in scratch
     # float32 and byte-swapped folds: folds per pass (0, default: what 1 GiB of part sums holds)
     "pfd_f32_chunk": 13,
+    "pfd_scrunch_direct": 14,  # scrunch calls: 0 rows that fit are summed in LDS (default), 1 one lane per bin
 }
 SOLVERS = {"pooled": 0, "batched": 1, "wave": 2}
 
@@ -209,6 +213,11 @@ class PfdKill(C.Structure):
     """pfe_pfd_kill: the killed parts (n x npart) and sub-bands (n x nsub) of a batch of folds,
     one byte each, non-zero = killed; either may be null."""
     _fields_ = [("parts", C.c_void_p), ("subs", C.c_void_p)]
+
+
+class PfdScrunchHow(C.Structure):
+    """pfe_pfd_scrunch_how: the rotation per (fold, channel), or null, and the two factors."""
+    _fields_ = [("rot", C.c_void_p), ("fscr", C.c_int32), ("bscr", C.c_int32)]
 
 
 class PhcxInfo(C.Structure):
@@ -300,6 +309,8 @@ def load_library(path: str | None = None) -> C.CDLL:
         pfd_kill = [vp, ptr(PfdIn), kill, vp, vp, u32]
         pfd_kill_f32 = [vp, ptr(PfdF32In), kill, vp, vp, u32]
         avg_kill = [vp, vp, i32, i32, i32, i64, kill, vp, i64, u32]
+        how = ptr(PfdScrunchHow)
+        scrunch = [vp, vp, i32, i32, i32, i64, how, vp, u32]
         signatures = {  # name: (restype, argtypes), as include/pfe.h and include/pfe_io.h declare
             "pfe_abi_version": (rc, []), "pfe_device_count": (rc, []),
             "pfe_create": (rc, [C.c_int, ptr(vp)]), "pfe_destroy": (None, [vp]),
@@ -334,6 +345,8 @@ def load_library(path: str | None = None) -> C.CDLL:
             "pfe_pfd_bates22_kill_f32": (rc, pfd_kill_f32), "pfe_pfd_params4_kill_f32": (rc, pfd_kill_f32),
             "pfe_pfd_dmfit4_kill_f32": (rc, pfd_kill_f32), "pfe_pfd_subband3_kill_f32": (rc, pfd_kill_f32),
             "pfe_pfd_avgprof_kill": (rc, avg_kill), "pfe_pfd_avgprof_kill_f32": (rc, avg_kill),
+            "pfe_pfd_scrunch": (rc, scrunch), "pfe_pfd_scrunch_f32": (rc, scrunch),
+            "pfe_pfd_scrunch_i16": (rc, [vp, ptr(PfdI16In), how, vp, u32]),
             "pfe_phcx_parse": (rc, [ptr(C.c_char_p), i64, i32, i32, ptr(vp)]),
             "pfe_phcx_count": (i64, [vp]),
             "pfe_phcx_info_get": (rc, [vp, i64, ptr(PhcxInfo)]),
@@ -1026,6 +1039,81 @@ class Engine:
             return out
         fn = self.lib.pfe_pfd_avgprof_f32 if f32 else self.lib.pfe_pfd_avgprof
         self._check(fn(self._h, _ptr(profs), npart, nsub, L, n, _ptr(out), 1, flags))
+        return out
+
+    def pfd_scrunch(self, profs, fscr=1, bscr=1, rot=None, scl=None, offs=None, wts=None,
+                    byteswapped=False, out=None):
+        """Scrunch a batch of folds (pfe_pfd_scrunch): profs (n,npart,nchan,nbin) float64, float32
+        (pfe_pfd_scrunch_f32) or int16 with scl, offs (and wts) as in pfd_dmprof
+        (pfe_pfd_scrunch_i16; byteswapped as there).  The parts of every element are summed, each
+        channel's row is rotated left by rot[i][c] mod nbin (rot: (n,nchan) or (nchan,) integers,
+        None = no rotation), bscr bins and then fscr channels are summed, each in order and in
+        fp64 (include/pfe.h states the steps).  Host arrays give a host array, device tensors (an
+        int16 cube may be strided views of an uploaded table) a device tensor: (n,1,G,K) float64,
+        G = nchan / fscr, K = nbin / bscr -- a fold of one part for the pfd_* calls, with
+        pfd.scrunch_plan's subfreqs, pfd.scrunch_scal's scalars and derive_avgprof=True."""
+        fn = "pfd_scrunch"
+        if profs.ndim != 4:
+            raise ValueError(f"{fn}: profs must be (n,npart,nchan,nbin)")
+        n, npart, nchan, nbin = profs.shape
+        fscr, bscr = int(fscr), int(bscr)
+        if fscr < 1 or bscr < 1:
+            raise ValueError(f"{fn}: fscr {fscr} and bscr {bscr} must be >= 1")
+        if nchan % fscr:
+            raise ValueError(f"{fn}: fscr {fscr} does not divide nchan {nchan}")
+        if nbin % bscr:
+            raise ValueError(f"{fn}: bscr {bscr} does not divide nbin {nbin}")
+        shape = (n, 1, nchan // fscr, nbin // bscr)
+        dev = _is_device(profs)
+        i16 = self._is_i16(profs)
+        if i16:
+            arrs = self._pfd_i16_arrays(fn, profs, scl, offs, wts)
+        elif scl is not None or offs is not None or wts is not None:
+            raise ValueError(f"{fn}: scl, offs and wts go with an int16 cube, profs is {profs.dtype}")
+        if dev:
+            import torch
+
+            if not i16:
+                self._dev(profs, "profs", (torch.float64, torch.float32))
+                f32 = profs.dtype == torch.float32
+            if rot is not None:
+                if tuple(rot.shape) not in ((nchan,), (n, nchan)):
+                    raise ValueError(f"{fn}: rot must be ({nchan},) or (n,{nchan}) = {(n, nchan)}")
+                rot = self._dev(rot.expand(n, nchan).contiguous(), "rot", (torch.int32,))
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float64, device=profs.device)
+            else:
+                self._dev(out, "out", (torch.float64,), shape=shape)
+            self._follow_torch()
+            flags = PFE_FLAG_DEVICE_PTRS
+        else:
+            if not i16:
+                f32 = isinstance(profs, np.ndarray) and profs.dtype == np.float32
+                profs = np.ascontiguousarray(profs, dtype=np.float32 if f32 else np.float64)
+            if rot is not None:
+                r = np.asarray(rot)
+                if r.dtype.kind not in "iu" or r.shape not in ((nchan,), (n, nchan)):
+                    raise ValueError(f"{fn}: rot must be integers, ({nchan},) or (n,{nchan}) = {(n, nchan)}")
+                if r.size and (r.min() < -2**31 or r.max() >= 2**31):
+                    raise ValueError(f"{fn}: rot must fit int32")
+                rot = np.ascontiguousarray(np.broadcast_to(r, (n, nchan)), dtype=np.int32)
+            if out is None:
+                out = np.empty(shape, dtype=np.float64)
+            elif (not isinstance(out, np.ndarray) or out.dtype != np.float64 or out.shape != shape
+                  or not out.flags.c_contiguous):
+                raise ValueError(f"{fn}: out must be a contiguous float64 array of shape {shape}")
+            flags = 0
+        if byteswapped:
+            flags |= PFE_FLAG_PFD_BSWAP
+        how = PfdScrunchHow(_ptr(rot) if rot is not None else None, fscr, bscr)
+        if i16:
+            pin = PfdI16In(_ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]),
+                           _ptr(arrs[3]) if arrs[3] is not None else None, arrs[4], arrs[5],
+                           None, None, npart, nchan, nbin, n)
+            self._check(self.lib.pfe_pfd_scrunch_i16(self._h, C.byref(pin), C.byref(how), _ptr(out), flags))
+        else:
+            call = self.lib.pfe_pfd_scrunch_f32 if f32 else self.lib.pfe_pfd_scrunch
+            self._check(call(self._h, _ptr(profs), npart, nchan, nbin, n, C.byref(how), _ptr(out), flags))
         return out
 
     def pfd_dmprof(self, profs, subfreqs, scal, profile=True, chis=True, lyon8=True,

@@ -19,7 +19,7 @@ LIB = os.path.join(LIBDIR, "libpfe.so")
 SOURCES = ["capi.hip", "lyon8.hip", "bates22.hip", "bates_sine_dm_sub.hip", "bates_gauss.hip", "bates_gauss_peel.hip",
            "bates_gauss_dg8.hip", "subband.hip", "subband_f64.hip",
            "pfd.hip", "pfd22.hip", "pfd_global.hip", "pfd_f32.hip", "cand_f32.hip",
-           "pfd_avgprof.hip", "pfd_be64.hip", "pfd_i16.hip", "pfd_kill.hip"]
+           "pfd_avgprof.hip", "pfd_be64.hip", "pfd_i16.hip", "pfd_kill.hip", "pfd_scrunch.hip"]
 # The Levenberg-Marquardt translation units are compiled without the two-address v_fmac_f64:
 # with it the register allocator copies the accumulator (a v_mov_b64 per fma whose addend
 # stays live -- every polynomial coefficient of exp, every Householder update), ~600 extra

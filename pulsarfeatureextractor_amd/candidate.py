@@ -332,6 +332,44 @@ class PFDFile(CandidateFileInterface):
         """PRESTO's pfd.kill_subbands: sub-bands that every later score leaves out."""
         self._killed(self.data.killed_subbands, subbands, self.data.nsub, "sub-band")
 
+    def scrunch(self, nsub=None, proflen=None):
+        """Replace the fold by its scrunched one-part form (Engine.pfd_scrunch): the parts
+        summed, the sub-bands summed in groups down to `nsub` -- each aligned at the fold's
+        bestdm on its group's centre (pfd.scrunch_plan), the groups left unaligned for the DM
+        search, as prepfold builds sub-bands from channels -- and the bins down to `proflen`.
+        None keeps a dimension.  subfreqs, binspersec and varprof become those of the new fold
+        (pfd.scrunch_scal), the average is derived on the device, and every later compute* /
+        get* call scores the scrunched fold.  Of the foldstats only prof_var (column 5, what
+        calc_varprof sums) is additive: the new (1, nsub, 7) array holds its sum over the parts
+        and the channels of a group times the bin factor, so that a later kill_subbands finds
+        its rows, and zeros in the other columns (averages, redchi: nothing here reads them).
+        chanpersub, subdeltafreq and losubfreq follow the new subfreqs.  A fold with killed rows
+        is refused: kill after scrunching."""
+        d = self.data
+        nsub = d.nsub if nsub is None else int(nsub)
+        proflen = d.proflen if proflen is None else int(proflen)
+        if nsub < 1 or d.nsub % nsub:
+            raise ValueError(f"scrunch: nsub {nsub} does not divide the fold's {d.nsub} sub-bands")
+        if proflen < 1 or d.proflen % proflen:
+            raise ValueError(f"scrunch: proflen {proflen} does not divide the fold's {d.proflen} bins")
+        if d.killed_intervals or d.killed_subbands:
+            raise ValueError("scrunch: the fold has killed rows; kill after scrunching")
+        fscr, bscr = d.nsub // nsub, d.proflen // proflen
+        rot, subfreqs = _pfd.scrunch_plan(d.subfreqs, d.bestdm, d.binspersec, d.proflen, fscr)
+        profs = np.ascontiguousarray(np.asarray(d.profs, dtype=np.float64)[None])
+        z = self.engine.pfd_scrunch(profs, fscr=fscr, bscr=bscr, rot=rot[None])
+        _, _, scal = self._batch()
+        scal = _pfd.scrunch_scal(scal, bscr)[0]
+        stats = np.zeros((1, nsub, 7))
+        stats[0, :, 5] = np.asarray(d.stats, dtype=np.float64)[:, :, 5].reshape(d.npart, nsub, fscr).sum(axis=(0, 2)) * bscr
+        new = dict(d.__dict__)
+        new.update(profs=z[0], stats=stats, npart=1, nsub=nsub, proflen=proflen, subfreqs=subfreqs,
+                   binspersec=float(scal[1]), varprof=float(scal[3]), avgprof=None,
+                   chanpersub=d.chanpersub * fscr, subdeltafreq=d.subdeltafreq * fscr,
+                   losubfreq=float(subfreqs[0]), killed_subbands=[], killed_intervals=[])
+        self.data = _pfd.PFDData(**new)
+        self._dmp = None
+
     def _dmprof(self):
         """pfe_pfd_dmprof of this fold (profile, chi^2 curve, Lyon features), launched once
         and shared by the profile / DM-curve / stat-score calls."""

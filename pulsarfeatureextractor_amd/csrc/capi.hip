@@ -331,6 +331,10 @@ int pfe_set_option(pfe_handle* h, int32_t option, int64_t v) {
       if (v < 0) break;
       o.pfd_f32_chunk = v;
       return PFE_OK;
+    case PFE_OPT_PFD_SCRUNCH_DIRECT:
+      if (v != 0 && v != 1) break;
+      o.pfd_scrunch_direct = (int)v;
+      return PFE_OK;
     default:
       return set_err(h, PFE_EINVAL, "pfe_set_option: unknown option %d", option);
   }
@@ -355,6 +359,7 @@ int pfe_get_option(const pfe_handle* h, int32_t option, int64_t* v) {
     case PFE_OPT_PFD_GLOBAL: *v = o.pfd_global; return PFE_OK;
     case PFE_OPT_SUBF64_GLOBAL: *v = o.subf64_global; return PFE_OK;
     case PFE_OPT_PFD_F32_CHUNK: *v = o.pfd_f32_chunk; return PFE_OK;
+    case PFE_OPT_PFD_SCRUNCH_DIRECT: *v = o.pfd_scrunch_direct; return PFE_OK;
     default: return PFE_EINVAL;
   }
 }
@@ -1389,6 +1394,114 @@ static int pfd_avgprof_i16_call(pfe_handle* h, const pfe_pfd_i16_in* in, double*
 int pfe_pfd_avgprof_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, int64_t out_stride,
                         uint32_t flags) {
   return pfd_avgprof_i16_call(h, in, out, out_stride, flags);
+}
+
+// pfe_pfd_scrunch (xd), pfe_pfd_scrunch_f32 (xf) and pfe_pfd_scrunch_i16 (i16: the four arrays,
+// the strides and the shape of the caller's struct; the shape arguments are then its own)
+static int pfd_scrunch_call(pfe_handle* h, const char* fn, const double* xd, const float* xf,
+                            bool f32, const pfe_pfd_i16_in* i16, int npart, int nchan, int nbin, int64_t n,
+                            const pfe_pfd_scrunch_how* how, double* out, uint32_t flags) {
+  if (!h) return PFE_EINVAL;
+  h->err.clear();
+  if (!how || !out) return set_err(h, PFE_EINVAL, "%s: null argument", fn);
+  if (n < 0) return set_err(h, PFE_EINVAL, "%s: n < 0", fn);
+  if (npart < 1 || nchan < 1 || nbin < 1)
+    return set_err(h, PFE_EINVAL, "%s: shape %dx%dx%d", fn, npart, nchan, nbin);
+  if (flags & PFE_FLAG_PFD_AVGPROF)
+    return set_err(h, PFE_EINVAL, "%s: PFE_FLAG_PFD_AVGPROF is for the calls that read scal", fn);
+  if (!i16 && (flags & PFE_FLAG_PFD_BSWAP))
+    return set_err(h, PFE_EINVAL, "%s: PFE_FLAG_PFD_BSWAP is for the _i16 form", fn);
+  if (how->fscr < 1 || how->bscr < 1)
+    return set_err(h, PFE_EINVAL, "%s: fscr %d and bscr %d must be >= 1", fn, how->fscr, how->bscr);
+  if (nchan % how->fscr)
+    return set_err(h, PFE_EINVAL, "%s: fscr %d does not divide nchan %d", fn, how->fscr, nchan);
+  if (nbin % how->bscr)
+    return set_err(h, PFE_EINVAL, "%s: bscr %d does not divide nbin %d", fn, how->bscr, nbin);
+  int rc;
+  if (i16) {
+    if ((rc = pfd_i16_check(h, fn, i16, flags, false))) return rc;
+  } else {
+    if (f32 ? !xf : !xd) return set_err(h, PFE_EINVAL, "%s: null input array", fn);
+    if (f32 ? ((uintptr_t)xf & 3) : ((uintptr_t)xd & 7))
+      return set_err(h, PFE_EINVAL, "%s: profs not %d-byte aligned", fn, f32 ? 4 : 8);
+  }
+  if ((uintptr_t)how->rot & 3) return set_err(h, PFE_EINVAL, "%s: rot not 4-byte aligned", fn);
+  if ((uintptr_t)out & 7) return set_err(h, PFE_EINVAL, "%s: out not 8-byte aligned", fn);
+  if (n == 0) return PFE_OK;
+  if ((rc = call_begin(h))) return rc;
+  const int64_t ES = (int64_t)npart * nchan, E = ES * nbin;
+  const int64_t GK = (int64_t)(nchan / how->fscr) * (nbin / how->bscr);
+  const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
+  pfe::PfdScrunchSrc x;
+  x.f64 = xd;
+  x.f32 = xf;
+  if (i16) x.i16 = pfe::pfd_i16_src(*i16, flags & PFE_FLAG_PFD_BSWAP);
+  const int32_t* rot = how->rot;
+  double* z = out;
+  if (host) {
+    pfe::PfdScrunchStage s;
+    rc = lay_out(h, s, [&](pfe::Arena& A) {
+      return pfe::pfd_scrunch_layout(
+          A, E, ES, nchan, GK, n, true, f32,
+          !i16 ? pfe::PFD_I16_NONE : i16->wts ? pfe::PFD_I16_WEIGHTS : pfe::PFD_I16_PLAIN,
+          rot != nullptr);
+    });
+    if (rc) return rc;
+    if (i16) {
+      if ((rc = stage_in(h, s.data16, i16->data, (size_t)n * E)) ||
+          (rc = stage_in(h, s.scl16, i16->scl, (size_t)n * ES)) ||
+          (rc = stage_in(h, s.offs16, i16->offs, (size_t)n * ES)) ||
+          (i16->wts && (rc = stage_in(h, s.wts16, i16->wts, (size_t)n * ES))))
+        return rc;
+      x.i16.data = reinterpret_cast<const char*>(s.data16);
+      x.i16.scl = reinterpret_cast<const char*>(s.scl16);
+      x.i16.offs = reinterpret_cast<const char*>(s.offs16);
+      if (i16->wts) x.i16.wts = reinterpret_cast<const char*>(s.wts16);
+    } else if (f32) {
+      if ((rc = stage_in(h, s.profs32, xf, (size_t)n * E))) return rc;
+      x.f32 = s.profs32;
+    } else {
+      if ((rc = stage_in(h, s.profs, xd, (size_t)n * E))) return rc;
+      x.f64 = s.profs;
+    }
+    if (rot) {
+      if ((rc = stage_in(h, s.rot, rot, (size_t)n * nchan))) return rc;
+      rot = s.rot;
+    }
+    z = s.out;
+  }
+  const hipError_t e = pfe::launch_pfd_scrunch(x, rot, z, npart, nchan, nbin, how->fscr, how->bscr, n,
+                                               h->opt.pfd_scrunch_direct != 0, h->stream);
+  if (e != hipSuccess) return set_err(h, PFE_EDEVICE, "%s launch: %s", fn, hipGetErrorString(e));
+  if (host) {
+    if ((rc = fetch(h, out, z, (size_t)n * GK))) return rc;
+    PFE_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return call_end(h);
+}
+
+int pfe_pfd_scrunch(pfe_handle* h, const double* profs, int32_t npart, int32_t nchan, int32_t nbin,
+                    int64_t n, const pfe_pfd_scrunch_how* how, double* out, uint32_t flags) {
+  return pfd_scrunch_call(h, "pfd_scrunch", profs, nullptr, false, nullptr, npart, nchan, nbin, n, how, out,
+                          flags);
+}
+
+int pfe_pfd_scrunch_f32(pfe_handle* h, const float* profs, int32_t npart, int32_t nchan,
+                        int32_t nbin, int64_t n, const pfe_pfd_scrunch_how* how, double* out,
+                        uint32_t flags) {
+  return pfd_scrunch_call(h, "pfd_scrunch_f32", nullptr, profs, true, nullptr, npart, nchan, nbin, n, how,
+                          out, flags);
+}
+
+int pfe_pfd_scrunch_i16(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_scrunch_how* how,
+                        double* out, uint32_t flags) {
+  if (h && !in) {
+    h->err.clear();
+    return set_err(h, PFE_EINVAL, "pfd_scrunch_i16: null argument");
+  }
+  if (!h) return PFE_EINVAL;
+  return pfd_scrunch_call(h, "pfd_scrunch_i16", nullptr, nullptr, false, in, in->npart, in->nsub, in->proflen,
+                          in->n, how, out, flags);
 }
 
 int pfe_pfd_dmprof_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* profile, float* chis,

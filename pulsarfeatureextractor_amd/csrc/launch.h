@@ -453,6 +453,66 @@ struct PfdKillSrc {
 hipError_t launch_pfd_partsum_kill(const void* x, int elem, const PfdKillSrc& k, double* s,
                                    int npart, int nsub, int L, int64_t n, hipStream_t st);
 
+// ---- scrunching a fold: pfe_pfd_scrunch and its _f32 / _i16 forms (pfd_scrunch.hip) ------
+// z[i][g][k], G = nchan / fscr groups of channels by K = nbin / bscr bins: the parts of every
+// element summed in order, each channel's row rotated left by rot[i][c] mod nbin, bscr bins
+// summed in order, fscr channels summed in order; all in fp64 (include/pfe.h states the steps).
+// Two routes, the same adds in the same order on both:
+//   LDS    (pfd_scrunch_lds: a row and the K running sums fit 64 KB of LDS) one block per (fold,
+//          group): slabs of `pfd_scrunch_slab_chans` channel rows are part-summed into the LDS with
+//          aligned wide loads, then K lanes add their bscr rotated values of every row in order;
+//   direct (any nbin) one lane per output bin, each value loaded alone at its rotated place.
+constexpr int PFD_SCR_LDS_DOUBLES = 8192;   // 64 KB: a row and the running sums of one block
+constexpr int PFD_SCR_SLAB_DOUBLES = 4096;  // 32 KB: the channel rows a block sums at a time
+inline bool pfd_scrunch_lds(int nbin, int bscr) {
+  return (((int64_t)nbin + 3) & ~(int64_t)3) + nbin / bscr <= PFD_SCR_LDS_DOUBLES;
+}
+inline int pfd_scrunch_slab_chans(int nbin, int fscr) {
+  const int c = PFD_SCR_SLAB_DOUBLES / nbin;
+  return c < 1 ? 1 : c > fscr ? fscr : c;
+}
+// the cube of a scrunch call: exactly one of f64, f32 and i16 (its data non-null) is set
+struct PfdScrunchSrc {
+  const double* f64 = nullptr;
+  const float* f32 = nullptr;
+  PfdI16Src i16;
+};
+// rot: n x nchan, or null; z: n x (nchan / fscr) x (nbin / bscr), dense.  direct: the direct
+// route whatever the shape (measurements and tests; a shape the LDS does not hold takes it anyway)
+hipError_t launch_pfd_scrunch(const PfdScrunchSrc& x, const int32_t* rot, double* z, int npart,
+                              int nchan, int nbin, int fscr, int bscr, int64_t n, bool direct,
+                              hipStream_t st);
+
+// pfe_pfd_scrunch / _f32 / _i16: a host-pointer call stages the cube as the values it holds (an
+// int16 cube with scl, offs and, when given, wts behind it: ES = npart x nchan floats a fold
+// each), then rot (n x nchan, when given), then out (n x GK doubles, GK = G x K).  A
+// device-pointer call takes no scratch
+struct PfdScrunchStage {
+  double* profs = nullptr;
+  float* profs32 = nullptr;
+  int16_t* data16 = nullptr;
+  float *scl16 = nullptr, *offs16 = nullptr, *wts16 = nullptr;
+  int32_t* rot = nullptr;
+  double* out = nullptr;
+};
+inline PfdScrunchStage pfd_scrunch_layout(Arena& A, int64_t E, int64_t ES, int nchan, int64_t GK,
+                                          int64_t n, bool host, bool f32, int i16, bool rot) {
+  PfdScrunchStage s;
+  if (!host) return s;
+  if (i16) {
+    s.data16 = A.take<int16_t>((size_t)n * E, "data16");
+    s.scl16 = A.take<float>((size_t)n * ES, "scl16");
+    s.offs16 = A.take<float>((size_t)n * ES, "offs16");
+    if (i16 == PFD_I16_WEIGHTS) s.wts16 = A.take<float>((size_t)n * ES, "wts16");
+  } else if (f32)
+    s.profs32 = A.take<float>((size_t)n * E, "profs32");
+  else
+    s.profs = A.take<double>((size_t)n * E, "profs");
+  if (rot) s.rot = A.take<int32_t>((size_t)n * nchan, "rot");
+  s.out = A.take<double>((size_t)n * GK, "out");
+  return s;
+}
+
 // ---- a fold's average: pfe_pfd_avgprof and PFE_FLAG_PFD_AVGPROF (pfd_avgprof.hip) --------
 // numpy's (profs / proflen).sum() of each fold: k_pfd_avgprof sums every chunk of
 // PFD_AVG_CHUNK values (numpy's reduction buffer) of a fold's E = npart x nsub x proflen into

@@ -26,6 +26,8 @@ struct Options {
                                    // scratch, 0 only the shapes that do not fit the LDS
   int64_t pfd_f32_chunk = 0;       // float32 folds: folds per pass (0: as many as 1 GiB of part
                                    // sums holds)
+  int pfd_scrunch_direct = 0;      // scrunch calls: 1 every shape on the direct route (one lane per
+                                   // output bin), 0 only the rows the LDS does not hold
 };
 
 }  // namespace pfe

@@ -174,6 +174,67 @@ def kill_masks(datas):
     return parts, subs
 
 
+def delay_from_dm(dm, freq):
+    """PFDOperations.delay_from_DM (:474-486): the dispersion delay in seconds at `freq` MHz,
+    0.0 where the frequency is not positive."""
+    freq = np.asarray(freq, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(freq > 0.0, dm / (0.000241 * freq * freq), 0.0)
+
+
+def scrunch_plan(chanfreqs, dm, binspersec, nbin, fscr):
+    """How Engine.pfd_scrunch makes sub-bands of fscr channels each, as prepfold does: the
+    channels of a group aligned at `dm` on the group's centre, the groups left unaligned for
+    the DM search.  chanfreqs (..., nchan) MHz, ascending or descending; dm and binspersec
+    scalars or (...,) -> (rot int32 (..., nchan), subfreqs (..., G)), G = nchan / fscr:
+      subfreqs[g] = 0.5 * (f[g*fscr] + f[g*fscr + fscr - 1])
+      rot[c]      = int(floor((delay(dm, f[c]) - delay(dm, subfreqs[g])) * binspersec + 0.5))
+    the left rotation of channel c in bins: positive below the centre (the pulse arrives later),
+    negative above it.  The device reduces it mod nbin; a value beyond int32 is reduced here."""
+    f = np.asarray(chanfreqs, dtype=np.float64)
+    fscr = int(fscr)
+    if f.ndim < 1 or fscr < 1 or f.shape[-1] % fscr:
+        raise ValueError(f"scrunch_plan: fscr {fscr} does not divide nchan "
+                         f"{f.shape[-1] if f.ndim else 0}")
+    if int(nbin) < 1:
+        raise ValueError(f"scrunch_plan: nbin {nbin}")
+    groups = f.reshape(f.shape[:-1] + (f.shape[-1] // fscr, fscr))
+    subfreqs = 0.5 * (groups[..., 0] + groups[..., -1])
+    dm = np.asarray(dm, dtype=np.float64)[..., None]
+    bps = np.asarray(binspersec, dtype=np.float64)[..., None]
+    lag = delay_from_dm(dm, f) - np.repeat(delay_from_dm(dm, subfreqs), fscr, axis=-1)
+    rot = np.floor(lag * bps + 0.5)
+    if not np.isfinite(rot).all():
+        raise ValueError("scrunch_plan: a rotation is not finite")
+    if rot.size and np.abs(rot).max() >= 2.0 ** 31:
+        rot = rot % float(nbin)
+    return rot.astype(np.int32), subfreqs
+
+
+def scrunch_route(nbin, bscr):
+    """The route the scrunch kernels take for rows of nbin bins summed bscr at a time
+    (csrc/launch.h pfd_scrunch_lds): 'lds' when a row, rounded up to a multiple of 4 values, and
+    its nbin / bscr running sums fit 8192 doubles of LDS, else 'direct' (one lane per output
+    bin).  The handle option pfd_scrunch_direct sends every shape the direct way; the bits are
+    the same on both."""
+    return "lds" if (int(nbin) + 3) // 4 * 4 + int(nbin) // int(bscr) <= 8192 else "direct"
+
+
+def scrunch_scal(scal, bscr):
+    """The scalars (..., 8) of a fold after Engine.pfd_scrunch summed bscr bins into one:
+    binspersec / bscr; varprof * bscr (a bin of the summed profile is the sum of bscr bins, so
+    its variance is bscr times a bin's); avgprof NaN, to be derived from the scrunched fold
+    (derive_avgprof=True).  The rest unchanged."""
+    bscr = int(bscr)
+    if bscr < 1:
+        raise ValueError(f"scrunch_scal: bscr {bscr}")
+    out = np.array(scal, dtype=np.float64)
+    out[..., 1] = out[..., 1] / bscr
+    out[..., 2] = np.nan
+    out[..., 3] = out[..., 3] * bscr
+    return out
+
+
 def write(path: str, *, profs, stats=None, dms, bestdm, fold_p1, bary_p1=None, lofreq=1200.0,
           chan_wid=1.0, numchan=None, dt=6.4e-5, big_endian=False, with_posn=True,
           periods=None, pdots=None):

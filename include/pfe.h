@@ -768,6 +768,67 @@ int pfe_pfd_scrunch_f32(pfe_handle* h, const float* profs, int32_t npart, int32_
 int pfe_pfd_scrunch_i16(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_scrunch_how* how,
                         double* out, uint32_t flags);
 
+/* ---- total intensity of int16 folds: polarisations summed where they are loaded ------------
+ * A fold-mode archive usually stores four polarisations per sub-integration (AABBCRCI) or two
+ * (AABB): its DATA cell is [npol][nchan][nbin] int16, DAT_SCL / DAT_OFFS are [npol][nchan]
+ * float32, DAT_WTS is [nchan] with no polarisation axis, and total intensity is AA + BB.  The
+ * _i16_pol forms of the seven calls that take pfe_pfd_i16_in score that sum, formed where the
+ * values are loaded; `pol` stands directly behind `in`, as `kill` does in the _kill forms.
+ *
+ * Layout.  The polarisation axis lies between part and sub-band, dense, for data and for scl /
+ * offs; wts has none:
+ *   value (i,p,k,s,b) of data        (char*)data + i*fold_stride + p*part_stride
+ *                                                + k*2*nsub*proflen + 2*(s*proflen + b)
+ *   value (i,p,k,s) of scl / offs    (char*)scl + i*fold_stride + p*part_stride + k*4*nsub + 4*s
+ *   value (i,p,s) of wts             as in the _i16 calls
+ * Both strides 0: dense arrays -- data n x npart x npol x nsub x proflen, scl and offs n x npart
+ * x npol x nsub, wts n x npart x nsub.  For a SUBINT table the four pointers are still the
+ * columns' addresses in row 0 and part_stride = NAXIS1.  The stride rule is part_stride >= 2 x
+ * npol x nsub x proflen; the other rules of the _i16 calls hold, their texts under the _i16_pol
+ * names.  PFE_EINVAL, the text naming the rule: npol outside 1..4, nsum outside 1..2, nsum > npol.
+ *
+ * Values.  Every output and the status is, bit for bit, that of the f64 call of the same name
+ * (pfe_pfd_scrunch for the scrunch) on the cube
+ *   y_k[p][s][b] = (double)d[p][k][s][b] * (double)scl[p][k][s] + (double)offs[p][k][s]   one rounding
+ *   x[p][s][b]   = y_0                  nsum = 1
+ *                = y_0 + y_1            nsum = 2: one more rounding
+ *   x[p][s][b]   = x * (double)wts[p][s]          wts given: one more rounding, on the sum
+ * In numpy: dec = d.astype(f8) * scl.astype(f8)[..., None] + offs.astype(f8)[..., None];
+ * x = dec[:, :, 0] + dec[:, :, 1]; x = x * wts.astype(f8)[..., None].  The weight multiplies the
+ * sum: one multiply per element.  That is not the sum of two weighted polarisations, y_0 w + y_1 w,
+ * which rounds twice more and differently.  From there on the _i16 contract holds: parts summed
+ * from part 0's value in order, the f64 kernels on the sums as folds of one part,
+ * PFE_FLAG_PFD_BSWAP reversing every 2- and 4-byte value in registers, PFE_FLAG_PFD_AVGPROF and
+ * pfe_pfd_avgprof_i16_pol giving numpy's (x / proflen).sum() of x in memory order (p, s, b); a NaN
+ * is a NaN, nothing is computed in float32 or integers, the inputs are never written.
+ * Polarisations nsum .. npol-1 are never read.  pol == NULL or {1, 1} is the _i16 call: the same
+ * kernels, the same scratch, the same bits.  nsum = 1 with npol > 1 runs those kernels too (only
+ * the strides know of npol), except on dense device arrays with weights, whose wts strides are
+ * not those of scl: there, and for nsum = 2, the polarisation forms of the kernels run.
+ * Scratch: a host-pointer call stages only what is read, compacted so the kernels see npol = nsum:
+ * data n x npart x nsum x nsub x proflen int16, scl and offs n x npart x nsum x nsub floats, wts
+ * as in the _i16 call; everything behind them is as for the _i16 call. */
+typedef struct pfe_pfd_i16_pol {
+  int32_t npol; /* polarisations stored per (fold, part): 1..4 */
+  int32_t nsum; /* leading polarisations summed: 1 or 2, <= npol */
+} pfe_pfd_i16_pol;
+
+int pfe_pfd_dmprof_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                           double* profile, float* chis, double* lyon8, uint32_t* status,
+                           uint32_t flags);
+int pfe_pfd_bates22_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                            double* out, uint32_t* status, uint32_t flags);
+int pfe_pfd_params4_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                            double* out, uint32_t* status, uint32_t flags);
+int pfe_pfd_dmfit4_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                           double* out, uint32_t* status, uint32_t flags);
+int pfe_pfd_subband3_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                             double* out, uint32_t* status, uint32_t flags);
+int pfe_pfd_avgprof_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                            double* out, int64_t out_stride, uint32_t flags);
+int pfe_pfd_scrunch_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                            const pfe_pfd_scrunch_how* how, double* out, uint32_t flags);
+
 /* ---- float32 candidates: the float-array calls on arrays of floats ----------------------
  * A candidate that never was a .pfd or .phcx file -- a float32 tensor from a GPU folder or a
  * normalising step, the arrays an ML pipeline keeps, the float32 DM curve pfe_pfd_dmprof

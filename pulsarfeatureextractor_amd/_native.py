@@ -74,6 +74,13 @@ EXPORTED_SYMBOLS = (
     "pfe_pfd_dmfit4_i16",
     "pfe_pfd_subband3_i16",
     "pfe_pfd_avgprof_i16",
+    "pfe_pfd_dmprof_i16_pol",
+    "pfe_pfd_bates22_i16_pol",
+    "pfe_pfd_params4_i16_pol",
+    "pfe_pfd_dmfit4_i16_pol",
+    "pfe_pfd_subband3_i16_pol",
+    "pfe_pfd_avgprof_i16_pol",
+    "pfe_pfd_scrunch_i16_pol",
     "pfe_pfd_dmprof_kill",
     "pfe_pfd_bates22_kill",
     "pfe_pfd_params4_kill",
@@ -209,6 +216,12 @@ class PfdI16In(C.Structure):
     ]
 
 
+class PfdI16Pol(C.Structure):
+    """pfe_pfd_i16_pol: the polarisations an int16 cube stores per (fold, part), 1..4, and the
+    leading ones that are summed, 1 or 2."""
+    _fields_ = [("npol", C.c_int32), ("nsum", C.c_int32)]
+
+
 class PfdKill(C.Structure):
     """pfe_pfd_kill: the killed parts (n x npart) and sub-bands (n x nsub) of a batch of folds,
     one byte each, non-zero = killed; either may be null."""
@@ -301,6 +314,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         pfd = [vp, ptr(PfdIn), vp, vp, u32]
         pfd_f32 = [vp, ptr(PfdF32In), vp, vp, u32]
         pfd_i16 = [vp, ptr(PfdI16In), vp, vp, u32]
+        pfd_i16_pol = [vp, ptr(PfdI16In), ptr(PfdI16Pol), vp, vp, u32]
         f64 = [vp, vp, i32, i64, vp, vp, u32]
         bates_f64 = [vp, ptr(BatesF64In), vp, vp, u32]
         bates_f32 = [vp, ptr(BatesF32In), vp, vp, u32]
@@ -338,6 +352,11 @@ def load_library(path: str | None = None) -> C.CDLL:
             "pfe_pfd_bates22_i16": (rc, pfd_i16), "pfe_pfd_params4_i16": (rc, pfd_i16),
             "pfe_pfd_dmfit4_i16": (rc, pfd_i16), "pfe_pfd_subband3_i16": (rc, pfd_i16),
             "pfe_pfd_avgprof_i16": (rc, [vp, ptr(PfdI16In), vp, i64, u32]),
+            "pfe_pfd_dmprof_i16_pol": (rc, [vp, ptr(PfdI16In), ptr(PfdI16Pol), vp, vp, vp, vp, u32]),
+            "pfe_pfd_bates22_i16_pol": (rc, pfd_i16_pol), "pfe_pfd_params4_i16_pol": (rc, pfd_i16_pol),
+            "pfe_pfd_dmfit4_i16_pol": (rc, pfd_i16_pol), "pfe_pfd_subband3_i16_pol": (rc, pfd_i16_pol),
+            "pfe_pfd_avgprof_i16_pol": (rc, [vp, ptr(PfdI16In), ptr(PfdI16Pol), vp, i64, u32]),
+            "pfe_pfd_scrunch_i16_pol": (rc, [vp, ptr(PfdI16In), ptr(PfdI16Pol), how, vp, u32]),
             "pfe_pfd_dmprof_kill": (rc, [vp, ptr(PfdIn), kill, vp, vp, vp, vp, u32]),
             "pfe_pfd_bates22_kill": (rc, pfd_kill), "pfe_pfd_params4_kill": (rc, pfd_kill),
             "pfe_pfd_dmfit4_kill": (rc, pfd_kill), "pfe_pfd_subband3_kill": (rc, pfd_kill),
@@ -847,17 +866,47 @@ class Engine:
             return profs.dtype == np.int16
         return str(getattr(profs, "dtype", "")) == "torch.int16"
 
+    @staticmethod
+    def _pfd_pol(fn, profs, pol_sum):
+        """The PfdI16Pol of a call, or None for a 4-D cube: pol_sum (the leading polarisations
+        summed, 1 or 2) is required with a (n,npart,npol,nsub,L) int16 cube, refused with any
+        other, and never guessed (an IQUV archive wants 1, an AABBCRCI one 2)."""
+        if profs.ndim != 5:
+            if pol_sum is not None:
+                raise ValueError(f"{fn}: pol_sum goes with a 5-D int16 cube (n,npart,npol,nsub,L), "
+                                 f"profs has {profs.ndim} dimensions")
+            return None
+        if not Engine._is_i16(profs):
+            raise ValueError(f"{fn}: a 5-D cube (n,npart,npol,nsub,L) must be int16, profs is {profs.dtype}")
+        if pol_sum is None:
+            raise ValueError(f"{fn}: pol_sum (1 or 2) is required with a 5-D int16 cube: the "
+                             "polarisations to sum are never guessed")
+        npol = int(profs.shape[2])
+        if pol_sum not in (1, 2):
+            raise ValueError(f"{fn}: pol_sum must be 1 or 2, got {pol_sum!r}")
+        if not 1 <= npol <= 4 or pol_sum > npol:
+            raise ValueError(f"{fn}: npol {npol} must be 1..4 and pol_sum {pol_sum} <= npol")
+        return PfdI16Pol(npol, int(pol_sum))
+
     def _pfd_i16_arrays(self, fn, profs, scl, offs, wts):
         """The four arrays of an int16 cube for pfe_pfd_i16_in -> (data, scl, offs, wts or None,
         fold_stride, part_stride): host arrays made dense; device tensors as they are -- all
         contiguous (strides 0, 0), or strided views of one uploaded table whose inner dimensions
-        are dense and whose byte strides agree."""
-        n, npart, nsub, L = profs.shape
+        are dense and whose byte strides agree.  A 5-D cube (n,npart,npol,nsub,L) goes with scl
+        and offs (n,npart,npol,nsub) and wts (n,npart,nsub): the polarisation axis counts among
+        the inner, dense dimensions of the cube, scl and offs."""
+        pol = profs.ndim == 5
+        n, npart = profs.shape[:2]
+        nsub, L = profs.shape[-2:]
         if scl is None or offs is None:
             raise ValueError(f"{fn}: scl and offs are required with an int16 cube")
         par = [("scl", scl), ("offs", offs)] + ([("wts", wts)] if wts is not None else [])
         for name, a in par:
-            if tuple(a.shape) != (n, npart, nsub):
+            if pol and name != "wts":
+                want = (n, npart, profs.shape[2], nsub)
+                if tuple(a.shape) != want:
+                    raise ValueError(f"{fn}: {name} must be (n,npart,npol,nsub) = {want}")
+            elif tuple(a.shape) != (n, npart, nsub):
                 raise ValueError(f"{fn}: {name} must be (n,npart,nsub) = {(n, npart, nsub)}")
         if not _is_device(profs):
             for name, a in [("profs", profs)] + par:
@@ -881,7 +930,11 @@ class Engine:
             if a.is_contiguous():
                 strides.add((0, 0))
                 continue
-            inner = (a.stride(3) == 1 and a.stride(2) == L) if name == "profs" else a.stride(2) == 1
+            want = 1  # the strides of dense inner dimensions, last to first
+            inner = True
+            for dim in range(a.ndim - 1, 1, -1):
+                inner = inner and a.stride(dim) == want
+                want *= a.shape[dim]
             if not inner:
                 raise ValueError(f"{fn}: {name}: the inner dimension{'s' if name == 'profs' else ''} "
                                  "of a strided view must be dense")
@@ -892,10 +945,11 @@ class Engine:
         fs, ps = strides.pop()
         return (profs, scl, offs, wts, fs, ps)
 
-    def _pfd_args(self, profs, subfreqs, scal, fn, scl=None, offs=None, wts=None):
-        if profs.ndim != 4:
+    def _pfd_args(self, profs, subfreqs, scal, fn, scl=None, offs=None, wts=None, pol=None):
+        if profs.ndim != (5 if pol is not None else 4):
             raise ValueError(f"{fn}: profs must be (n,npart,nsub,L)")
-        n, npart, nsub, L = profs.shape
+        n, npart = profs.shape[:2]
+        nsub, L = profs.shape[-2:]
         if tuple(subfreqs.shape) != (n, nsub) or tuple(scal.shape) != (n, PFE_PFD_NSCAL):
             raise ValueError(f"{fn}: subfreqs must be (n,nsub), scal (n,{PFE_PFD_NSCAL})")
         dev = _is_device(profs)
@@ -933,10 +987,14 @@ class Engine:
         pin = (PfdF32In if f32 else PfdIn)(_ptr(profs), _ptr(subfreqs), _ptr(scal), npart, nsub, L, n)
         return pin, dev, (profs, subfreqs, scal)
 
-    def _pfd_fn(self, fn, pin, kill=None):
+    def _pfd_fn(self, fn, pin, kill=None, pol=None):
         """The C entry point of a PFD call: its _f32 form for a float32 cube, its _i16 form for
-        an int16 one; with masks (kill: a PfdKill) its _kill form, the masks behind `in`."""
+        an int16 one; with masks (kill: a PfdKill) its _kill form, the masks behind `in`; with
+        polarisations (pol: a PfdI16Pol) its _i16_pol form, pol behind `in`."""
         sfx = "_f32" if isinstance(pin, PfdF32In) else "_i16" if isinstance(pin, PfdI16In) else ""
+        if pol is not None:
+            f = getattr(self.lib, "pfe_" + fn + "_i16_pol")
+            return lambda h, pin_ref, *rest: f(h, pin_ref, C.byref(pol), *rest)
         if kill is None:
             return getattr(self.lib, "pfe_" + fn + sfx)
         f = getattr(self.lib, "pfe_" + fn + "_kill" + sfx)
@@ -949,7 +1007,7 @@ class Engine:
         torch.uint8 tensors on the cube's device for a device cube."""
         if kill_parts is None and kill_subs is None:
             return None, None
-        if profs.ndim != 4:
+        if profs.ndim != 4 and not (profs.ndim == 5 and self._is_i16(profs)):
             raise ValueError(f"{fn}: profs must be (n,npart,nsub,L)")
         if self._is_i16(profs):
             raise ValueError(f"{fn}: kill_parts and kill_subs are for float cubes; an int16 cube "
@@ -984,18 +1042,20 @@ class Engine:
         return kill, keep
 
     def pfd_avgprof(self, profs, byteswapped=False, scl=None, offs=None, wts=None,
-                    kill_parts=None, kill_subs=None):
+                    kill_parts=None, kill_subs=None, pol_sum=None):
         """numpy's (profs / proflen).sum() of each fold of a (n,npart,nsub,L) cube, bit for
         bit (pfe_pfd_avgprof; a float32 cube -- numpy array or device tensor -- goes to
         pfe_pfd_avgprof_f32 as it is and gives the value of profs.astype(float64)): the
         scal[:, 2] every PFD call reads.  byteswapped: as in pfd_dmprof.  An int16 cube with scl,
         offs (and wts) as in pfd_dmprof goes to pfe_pfd_avgprof_i16 and gives the value of the
         decoded cube.  kill_parts, kill_subs: as in pfd_dmprof; the value is that of the zapped
-        cube np.where(kill, 0.0, profs) (pfe_pfd_avgprof_kill).  Returns (n,) float64 where the
-        cube lives."""
-        if profs.ndim != 4:
+        cube np.where(kill, 0.0, profs) (pfe_pfd_avgprof_kill).  pol_sum with a 5-D int16 cube:
+        as in pfd_dmprof (pfe_pfd_avgprof_i16_pol).  Returns (n,) float64 where the cube lives."""
+        pol = self._pfd_pol("pfd_avgprof", profs, pol_sum)
+        if profs.ndim != 4 and pol is None:
             raise ValueError("pfd_avgprof: profs must be (n,npart,nsub,L)")
-        n, npart, nsub, L = profs.shape
+        n, npart = profs.shape[:2]
+        nsub, L = profs.shape[-2:]
         kill, kkeep = self._pfd_kill("pfd_avgprof", profs, kill_parts, kill_subs)
         if self._is_i16(profs):
             arrs = self._pfd_i16_arrays("pfd_avgprof", profs, scl, offs, wts)
@@ -1013,7 +1073,11 @@ class Engine:
             pin = PfdI16In(_ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]),
                            _ptr(arrs[3]) if arrs[3] is not None else None, arrs[4], arrs[5],
                            None, None, npart, nsub, L, n)
-            self._check(self.lib.pfe_pfd_avgprof_i16(self._h, C.byref(pin), _ptr(out), 1, flags))
+            if pol is not None:
+                self._check(self.lib.pfe_pfd_avgprof_i16_pol(self._h, C.byref(pin), C.byref(pol),
+                                                             _ptr(out), 1, flags))
+            else:
+                self._check(self.lib.pfe_pfd_avgprof_i16(self._h, C.byref(pin), _ptr(out), 1, flags))
             return out
         if scl is not None or offs is not None or wts is not None:
             raise ValueError(f"pfd_avgprof: scl, offs and wts go with an int16 cube, profs is {profs.dtype}")
@@ -1042,7 +1106,7 @@ class Engine:
         return out
 
     def pfd_scrunch(self, profs, fscr=1, bscr=1, rot=None, scl=None, offs=None, wts=None,
-                    byteswapped=False, out=None):
+                    byteswapped=False, out=None, pol_sum=None):
         """Scrunch a batch of folds (pfe_pfd_scrunch): profs (n,npart,nchan,nbin) float64, float32
         (pfe_pfd_scrunch_f32) or int16 with scl, offs (and wts) as in pfd_dmprof
         (pfe_pfd_scrunch_i16; byteswapped as there).  The parts of every element are summed, each
@@ -1051,11 +1115,15 @@ class Engine:
         fp64 (include/pfe.h states the steps).  Host arrays give a host array, device tensors (an
         int16 cube may be strided views of an uploaded table) a device tensor: (n,1,G,K) float64,
         G = nchan / fscr, K = nbin / bscr -- a fold of one part for the pfd_* calls, with
-        pfd.scrunch_plan's subfreqs, pfd.scrunch_scal's scalars and derive_avgprof=True."""
+        pfd.scrunch_plan's subfreqs, pfd.scrunch_scal's scalars and derive_avgprof=True.
+        pol_sum with a 5-D int16 cube (n,npart,npol,nchan,nbin): as in pfd_dmprof
+        (pfe_pfd_scrunch_i16_pol)."""
         fn = "pfd_scrunch"
-        if profs.ndim != 4:
+        pol = self._pfd_pol(fn, profs, pol_sum)
+        if profs.ndim != 4 and pol is None:
             raise ValueError(f"{fn}: profs must be (n,npart,nchan,nbin)")
-        n, npart, nchan, nbin = profs.shape
+        n, npart = profs.shape[:2]
+        nchan, nbin = profs.shape[-2:]
         fscr, bscr = int(fscr), int(bscr)
         if fscr < 1 or bscr < 1:
             raise ValueError(f"{fn}: fscr {fscr} and bscr {bscr} must be >= 1")
@@ -1110,7 +1178,11 @@ class Engine:
             pin = PfdI16In(_ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]),
                            _ptr(arrs[3]) if arrs[3] is not None else None, arrs[4], arrs[5],
                            None, None, npart, nchan, nbin, n)
-            self._check(self.lib.pfe_pfd_scrunch_i16(self._h, C.byref(pin), C.byref(how), _ptr(out), flags))
+            if pol is not None:
+                self._check(self.lib.pfe_pfd_scrunch_i16_pol(self._h, C.byref(pin), C.byref(pol),
+                                                             C.byref(how), _ptr(out), flags))
+            else:
+                self._check(self.lib.pfe_pfd_scrunch_i16(self._h, C.byref(pin), C.byref(how), _ptr(out), flags))
         else:
             call = self.lib.pfe_pfd_scrunch_f32 if f32 else self.lib.pfe_pfd_scrunch
             self._check(call(self._h, _ptr(profs), npart, nchan, nbin, n, C.byref(how), _ptr(out), flags))
@@ -1118,7 +1190,7 @@ class Engine:
 
     def pfd_dmprof(self, profs, subfreqs, scal, profile=True, chis=True, lyon8=True,
                    derive_avgprof=False, byteswapped=False, scl=None, offs=None, wts=None,
-                   kill_parts=None, kill_subs=None):
+                   kill_parts=None, kill_subs=None, pol_sum=None):
         """PFD preprocessing + Lyon features (pfe_pfd_dmprof) for a batch of folds of one
         shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL).
         A float32 cube (numpy array or device tensor) is scored as it is, by the _f32 call of
@@ -1146,9 +1218,19 @@ class Engine:
         scal[:, 2] and scal[:, 3] must be those of the zapped fold (pfd.varprof; derive_avgprof
         derives the average of the zapped cube).  With an int16 cube they are a ValueError: there
         wts = 0 is the kill.  Both None: the plain call.
+        pol_sum (this and the other PFD methods, pfd_avgprof and pfd_scrunch): an int16 cube with a
+        polarisation axis, (n,npart,npol,nsub,L) with scl and offs (n,npart,npol,nsub) and wts
+        (n,npart,nsub), is scored as total intensity by the _i16_pol call: pol_sum = 2 sums the
+        first two polarisations (AA + BB of an AABB or AABBCRCI archive), 1 reads the first alone
+        (I of IQUV); the others are never read.  The result is the bits of the f64 call on
+        dec[:, :, 0] + dec[:, :, 1] (pol_sum = 2), dec the decoded cube, times wts when given --
+        the weight multiplies the sum.  pol_sum is required with a 5-D cube, refused with a 4-D
+        one, never guessed.  Device tensors may be strided views of one uploaded table: the inner
+        three dimensions of the cube and the inner two of scl and offs dense.
         Returns dict(profile (n,L) f64, chis (n,100) f32, lyon8 (n,8) f64, status (n,))."""
+        pol = self._pfd_pol("pfd_dmprof", profs, pol_sum)
         kill, kkeep = self._pfd_kill("pfd_dmprof", profs, kill_parts, kill_subs)
-        pin, dev, keep = self._pfd_args(profs, subfreqs, scal, "pfd_dmprof", scl, offs, wts)
+        pin, dev, keep = self._pfd_args(profs, subfreqs, scal, "pfd_dmprof", scl, offs, wts, pol)
         n, L = pin.n, pin.proflen
         out = {}
         if dev:
@@ -1169,7 +1251,7 @@ class Engine:
         out["chis"] = mk((n, PFE_PFD_NDM), f32) if chis else None
         out["lyon8"] = mk((n, 8), f64) if lyon8 else None
         out["status"] = mk((n,), i32)
-        self._check(self._pfd_fn("pfd_dmprof", pin, kill)(
+        self._check(self._pfd_fn("pfd_dmprof", pin, kill, pol)(
             self._h, C.byref(pin), _ptr(out["profile"]) if profile else None,
             _ptr(out["chis"]) if chis else None, _ptr(out["lyon8"]) if lyon8 else None,
             _ptr(out["status"]), flags))
@@ -1178,48 +1260,49 @@ class Engine:
 
     def _pfd_scores(self, fn, k, profs, subfreqs, scal, out, status, derive_avgprof=False,
                     byteswapped=False, scl=None, offs=None, wts=None, kill_parts=None,
-                    kill_subs=None):
+                    kill_subs=None, pol_sum=None):
+        pol = self._pfd_pol(fn, profs, pol_sum)
         kill, kkeep = self._pfd_kill(fn, profs, kill_parts, kill_subs)
-        pin, dev, keep = self._pfd_args(profs, subfreqs, scal, fn, scl, offs, wts)
+        pin, dev, keep = self._pfd_args(profs, subfreqs, scal, fn, scl, offs, wts, pol)
         out, status, flags = self._outputs(dev, profs, pin.n, k, out, status)
         if derive_avgprof:
             flags |= PFE_FLAG_PFD_AVGPROF
         if byteswapped:
             flags |= PFE_FLAG_PFD_BSWAP
-        self._check(self._pfd_fn(fn, pin, kill)(self._h, C.byref(pin), _ptr(out), _ptr(status), flags))
+        self._check(self._pfd_fn(fn, pin, kill, pol)(self._h, C.byref(pin), _ptr(out), _ptr(status), flags))
         del keep, kkeep
         return out, status
 
     def pfd_bates22(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
                     byteswapped=False, scl=None, offs=None, wts=None, kill_parts=None,
-                    kill_subs=None):
+                    kill_subs=None, pol_sum=None):
         """The 22 scores of PFD folds (pfe_pfd_bates22, PFDFile.compute) for a batch of one
         shape: profs (n,npart,nsub,L) f64, subfreqs (n,nsub), scal (n,PFE_PFD_NSCAL) with
         scal[:, 7] = bary_p1.  Returns (out (n,22) f64, status (n,))."""
         return self._pfd_scores("pfd_bates22", 22, profs, subfreqs, scal, out, status,
-                                derive_avgprof, byteswapped, scl, offs, wts, kill_parts, kill_subs)
+                                derive_avgprof, byteswapped, scl, offs, wts, kill_parts, kill_subs, pol_sum)
 
     # one score group of a batch of folds (PFDOperations; inputs as pfd_bates22)
     def pfd_params4(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
                     byteswapped=False, scl=None, offs=None, wts=None, kill_parts=None,
-                    kill_subs=None):
+                    kill_subs=None, pol_sum=None):
         """getCandidateParameters (pfe_pfd_params4): [period_ms, snr, dm, width], unfiltered."""
         return self._pfd_scores("pfd_params4", 4, profs, subfreqs, scal, out, status,
-                                derive_avgprof, byteswapped, scl, offs, wts, kill_parts, kill_subs)
+                                derive_avgprof, byteswapped, scl, offs, wts, kill_parts, kill_subs, pol_sum)
 
     def pfd_dmfit4(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
                    byteswapped=False, scl=None, offs=None, wts=None, kill_parts=None,
-                   kill_subs=None):
+                   kill_subs=None, pol_sum=None):
         """getDMFittings (pfe_pfd_dmfit4): [s16, s17, Shift (signed), s19]."""
         return self._pfd_scores("pfd_dmfit4", 4, profs, subfreqs, scal, out, status,
-                                derive_avgprof, byteswapped, scl, offs, wts, kill_parts, kill_subs)
+                                derive_avgprof, byteswapped, scl, offs, wts, kill_parts, kill_subs, pol_sum)
 
     def pfd_subband3(self, profs, subfreqs, scal, out=None, status=None, derive_avgprof=False,
                      byteswapped=False, scl=None, offs=None, wts=None, kill_parts=None,
-                     kill_subs=None):
+                     kill_subs=None, pol_sum=None):
         """getSubbandParameters (pfe_pfd_subband3): s20-s22."""
         return self._pfd_scores("pfd_subband3", 3, profs, subfreqs, scal, out, status,
-                                derive_avgprof, byteswapped, scl, offs, wts, kill_parts, kill_subs)
+                                derive_avgprof, byteswapped, scl, offs, wts, kill_parts, kill_subs, pol_sum)
 
 
 class PhcxBatch:

@@ -947,23 +947,51 @@ static pfe::PfdArgs pfd_args(const pfe_handle* h, const pfe_pfd_in* in) {
   a.waves = h->opt.pfd_waves;
   return a;
 }
+// host path of every int16 call: the dense arrays of q (n folds of npart parts of npol
+// polarisations of nsub x L values) into their regions, and q reads them there.  Only the q.nsum
+// leading polarisations, the ones that are read, are staged, compacted -- one pitched copy an
+// array when npol > nsum -- so the kernels see a dense cube of npol = nsum; wts has no such axis
+static int stage_i16(pfe_handle* h, pfe::PfdI16Src& q, int16_t* data16, float* scl16, float* offs16,
+                     float* wts16, int64_t n, int npart, int nsub, int L, int npol) {
+  const size_t rows = (size_t)n * npart, ns = (size_t)q.nsum;
+  const size_t drow = (size_t)nsub * L * sizeof(int16_t), prow = (size_t)nsub * sizeof(float);
+  int rc;
+  if (npol == q.nsum) {
+    if ((rc = stage_in(h, data16, q.data, rows * ns * nsub * L)) ||
+        (rc = stage_in(h, scl16, q.scl, rows * ns * nsub)) ||
+        (rc = stage_in(h, offs16, q.offs, rows * ns * nsub)))
+      return rc;
+  } else {
+    PFE_HIP(h, hipMemcpy2DAsync(data16, ns * drow, q.data, npol * drow, ns * drow, rows,
+                                hipMemcpyHostToDevice, h->stream));
+    PFE_HIP(h, hipMemcpy2DAsync(scl16, ns * prow, q.scl, npol * prow, ns * prow, rows,
+                                hipMemcpyHostToDevice, h->stream));
+    PFE_HIP(h, hipMemcpy2DAsync(offs16, ns * prow, q.offs, npol * prow, ns * prow, rows,
+                                hipMemcpyHostToDevice, h->stream));
+  }
+  if (q.wts && (rc = stage_in(h, wts16, q.wts, rows * nsub))) return rc;
+  q.data = reinterpret_cast<const char*>(data16);
+  q.scl = reinterpret_cast<const char*>(scl16);
+  q.offs = reinterpret_cast<const char*>(offs16);
+  if (q.wts) q.wts = reinterpret_cast<const char*>(wts16);
+  q.dps = q.dks * (int64_t)ns;
+  q.dfs = q.dps * npart;
+  q.pps = q.pks * (int64_t)ns;
+  q.pfs = q.pps * npart;
+  return PFE_OK;
+}
 // host path: the three inputs into their regions `d`, and `a` reads them there (x32: the
 // float cube of an _f32 call, copied as the floats it is; q: the dense int16 cube of an _i16
-// call and its parameters, copied as they are; each pass points a.profs at its sums)
+// call and its parameters, copied as they are, npol polarisations a part of which stage_i16
+// takes those that are read; each pass points a.profs at its sums)
 static int stage_pfd(pfe_handle* h, const pfe_pfd_in* in, const float*& x32, pfe::PfdI16Src* q,
-                     const pfe::PfdInputs& d, pfe::PfdArgs& a) {
+                     const pfe::PfdInputs& d, pfe::PfdArgs& a, int npol = 1) {
   const size_t n = (size_t)in->n, cube = n * in->npart * in->nsub * in->proflen;
-  const size_t par = n * in->npart * in->nsub;
   int rc;
   if (q) {
-    if ((rc = stage_in(h, d.data16, q->data, cube)) || (rc = stage_in(h, d.scl16, q->scl, par)) ||
-        (rc = stage_in(h, d.offs16, q->offs, par)) ||
-        (q->wts && (rc = stage_in(h, d.wts16, q->wts, par))))
+    if ((rc = stage_i16(h, *q, d.data16, d.scl16, d.offs16, d.wts16, in->n, in->npart, in->nsub,
+                        in->proflen, npol)))
       return rc;
-    q->data = reinterpret_cast<const char*>(d.data16);
-    q->scl = reinterpret_cast<const char*>(d.scl16);
-    q->offs = reinterpret_cast<const char*>(d.offs16);
-    if (q->wts) q->wts = reinterpret_cast<const char*>(d.wts16);
   } else if ((rc = x32 ? stage_in(h, d.profs32, x32, cube) : stage_in(h, d.profs, in->profs, cube))) {
     return rc;
   }
@@ -999,12 +1027,15 @@ struct PfdF32View {
 };
 // The pfe_pfd_*_i16 calls go through the bodies of the f64 calls as well: `in` without its
 // cube, the four arrays and their strides beside it (q: null as the caller's `in` was)
+// The polarisations of an _i16_pol call: NULL is {1, 1}, the _i16 call
+static int pfd_npol(const pfe_pfd_i16_pol* pol) { return pol ? pol->npol : 1; }
+static int pfd_nsum(const pfe_pfd_i16_pol* pol) { return pol ? pol->nsum : 1; }
 struct PfdI16View {
   pfe_pfd_in in{};
   pfe::PfdI16Src src;
   const pfe_pfd_in* view = nullptr;
   pfe::PfdI16Src* q = nullptr;
-  PfdI16View(const pfe_pfd_i16_in* f, uint32_t flags) {
+  PfdI16View(const pfe_pfd_i16_in* f, uint32_t flags, const pfe_pfd_i16_pol* pol = nullptr) {
     if (!f) return;
     in.subfreqs = f->subfreqs;
     in.scal = f->scal;
@@ -1012,15 +1043,26 @@ struct PfdI16View {
     in.nsub = f->nsub;
     in.proflen = f->proflen;
     in.n = f->n;
-    src = pfe::pfd_i16_src(*f, flags & PFE_FLAG_PFD_BSWAP);
+    src = pfe::pfd_i16_src(*f, flags & PFE_FLAG_PFD_BSWAP, pfd_npol(pol), pfd_nsum(pol));
     view = &in;
     q = &src;
   }
 };
 // the four arrays and the strides of an _i16 call, each rule of include/pfe.h by its name
-// (the shape is positive: the caller's shape check has run)
+// (the shape is positive: the caller's shape check has run); pol: the polarisations of an
+// _i16_pol call (null: one), whose rules come first
 static int pfd_i16_check(pfe_handle* h, const char* fn, const pfe_pfd_i16_in* f, uint32_t flags,
-                         bool arrays) {
+                         bool arrays, const pfe_pfd_i16_pol* pol = nullptr) {
+  if (pol) {
+    if (pol->npol < 1 || pol->npol > 4)
+      return set_err(h, PFE_EINVAL, "%s: npol %d: polarisations stored per (fold, part) must be 1..4", fn,
+                     pol->npol);
+    if (pol->nsum < 1 || pol->nsum > 2)
+      return set_err(h, PFE_EINVAL, "%s: nsum %d: polarisations summed must be 1 or 2", fn, pol->nsum);
+    if (pol->nsum > pol->npol)
+      return set_err(h, PFE_EINVAL, "%s: nsum %d must be <= npol %d", fn, pol->nsum, pol->npol);
+  }
+  const int npol = pfd_npol(pol);
   if (!f->data || !f->scl || !f->offs || (arrays && (!f->subfreqs || !f->scal)))
     return set_err(h, PFE_EINVAL, "%s: null input array", fn);
   if ((uintptr_t)f->data & 1) return set_err(h, PFE_EINVAL, "%s: data not 2-byte aligned", fn);
@@ -1036,11 +1078,10 @@ static int pfd_i16_check(pfe_handle* h, const char* fn, const pfe_pfd_i16_in* f,
     return set_err(h, PFE_EINVAL,
                    "%s: strided input is for device pointers (PFE_FLAG_DEVICE_PTRS); a host-pointer "
                    "call takes dense arrays (both strides 0)", fn);
-  const int64_t row = (int64_t)2 * f->nsub * f->proflen;
+  const int64_t row = (int64_t)2 * npol * f->nsub * f->proflen;
   if (ps < row || ps % 4)
-    return set_err(h, PFE_EINVAL,
-                   "%s: part_stride %lld must be >= 2 x nsub x proflen = %lld and a multiple of 4", fn,
-                   (long long)ps, (long long)row);
+    return set_err(h, PFE_EINVAL, "%s: part_stride %lld must be >= 2 x %snsub x proflen = %lld and a multiple of 4",
+                   fn, (long long)ps, pol ? "npol x " : "", (long long)row);
   if (fs % 4 || fs / ps < f->npart)
     return set_err(h, PFE_EINVAL,
                    "%s: fold_stride %lld must be >= npart x part_stride = %d x %lld and a multiple of 4",
@@ -1160,15 +1201,19 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
                            double* profile, float* chis, double* lyon8, uint32_t* status,
                            uint32_t flags, const pfe_pfd_i16_in* i16 = nullptr,
                            pfe::PfdI16Src* q = nullptr, bool kcall = false,
-                           const pfe_pfd_kill* kill = nullptr) {
-  const char* fn = q ? "pfd_dmprof_i16" : kcall ? "pfd_dmprof_kill" : "pfd_dmprof";
+                           const pfe_pfd_kill* kill = nullptr, bool polcall = false,
+                           const pfe_pfd_i16_pol* pol = nullptr) {
+  const char* fn = polcall ? "pfd_dmprof_i16_pol"
+                   : q     ? "pfd_dmprof_i16"
+                   : kcall ? "pfd_dmprof_kill"
+                           : "pfd_dmprof";
   int64_t n;
   int rc = call_check(h, fn, in, status != nullptr, n);
   if (rc || n == 0) return rc;
   if (!q && (rc = pfd_cube_check(h, fn, in, f32, x32, flags))) return rc;
   if (in->npart < 1 || in->nsub < 1 || in->proflen < 2)
     return set_err(h, PFE_EINVAL, "%s: shape %dx%dx%d", fn, in->npart, in->nsub, in->proflen);
-  if (q && (rc = pfd_i16_check(h, fn, i16, flags, true))) return rc;
+  if (q && (rc = pfd_i16_check(h, fn, i16, flags, true, pol))) return rc;
   const bool useg = pfd_use_global(h, in);
   if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
     return pfd_shape_err(h, fn, in);
@@ -1202,9 +1247,9 @@ static int pfd_dmprof_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   pfe::PfdDmprofStage s;
   rc = lay_out(h, s, [&](pfe::Arena& A) {
     return pfe::pfd_dmprof_layout(A, *in, host, profile, chis, lyon8, ws_bytes, sums ? pass : 0,
-                                  derive, be || (killed && !f32), ki, kmask.mask());
+                                  derive, be || (killed && !f32), ki, kmask.mask(), pfd_nsum(pol));
   });
-  if (rc || (host && (rc = stage_pfd(h, in, x32, q, s.in, a)))) return rc;
+  if (rc || (host && (rc = stage_pfd(h, in, x32, q, s.in, a, pfd_npol(pol))))) return rc;
   if (host && killed && (rc = stage_kill(h, kmask, s.in.kparts, s.in.ksubs, n, in->npart, in->nsub)))
     return rc;
   double* wscal = nullptr;
@@ -1336,9 +1381,11 @@ int pfe_pfd_avgprof_kill_f32(pfe_handle* h, const float* profs, int32_t npart, i
 }
 
 // pfe_pfd_avgprof_i16: the four arrays, the strides and the shape of `in` only
+// and pfe_pfd_avgprof_i16_pol (polcall; pol: the caller's polarisations, or null)
 static int pfd_avgprof_i16_call(pfe_handle* h, const pfe_pfd_i16_in* in, double* out,
-                                int64_t out_stride, uint32_t flags) {
-  const char* fn = "pfd_avgprof_i16";
+                                int64_t out_stride, uint32_t flags, bool polcall = false,
+                                const pfe_pfd_i16_pol* pol = nullptr) {
+  const char* fn = polcall ? "pfd_avgprof_i16_pol" : "pfd_avgprof_i16";
   if (!h) return PFE_EINVAL;
   h->err.clear();
   if (!in || !out) return set_err(h, PFE_EINVAL, "%s: null argument", fn);
@@ -1347,29 +1394,22 @@ static int pfd_avgprof_i16_call(pfe_handle* h, const pfe_pfd_i16_in* in, double*
   if (in->npart < 1 || in->nsub < 1 || in->proflen < 2)
     return set_err(h, PFE_EINVAL, "%s: shape %dx%dx%d", fn, in->npart, in->nsub, in->proflen);
   if (out_stride < 1) return set_err(h, PFE_EINVAL, "%s: out_stride < 1", fn);
-  int rc = pfd_i16_check(h, fn, in, flags, false);
+  int rc = pfd_i16_check(h, fn, in, flags, false, pol);
   if (rc || n == 0) return rc;
   if ((rc = call_begin(h))) return rc;
   const int64_t ES = (int64_t)in->npart * in->nsub, E = ES * in->proflen;
   const bool host = !(flags & PFE_FLAG_DEVICE_PTRS);
-  pfe::PfdI16Src q = pfe::pfd_i16_src(*in, flags & PFE_FLAG_PFD_BSWAP);
+  pfe::PfdI16Src q = pfe::pfd_i16_src(*in, flags & PFE_FLAG_PFD_BSWAP, pfd_npol(pol), pfd_nsum(pol));
   pfe::PfdAvgStage s;
   rc = lay_out(h, s, [&](pfe::Arena& A) {
     return pfe::pfd_avgprof_layout(A, E, n, host, false,
-                                   in->wts ? pfe::PFD_I16_WEIGHTS : pfe::PFD_I16_PLAIN, ES);
+                                   in->wts ? pfe::PFD_I16_WEIGHTS : pfe::PFD_I16_PLAIN, ES, 0, 0, 0,
+                                   pfd_nsum(pol));
   });
   if (rc) return rc;
-  if (host) {
-    if ((rc = stage_in(h, s.data16, in->data, (size_t)n * E)) ||
-        (rc = stage_in(h, s.scl16, in->scl, (size_t)n * ES)) ||
-        (rc = stage_in(h, s.offs16, in->offs, (size_t)n * ES)) ||
-        (in->wts && (rc = stage_in(h, s.wts16, in->wts, (size_t)n * ES))))
-      return rc;
-    q.data = reinterpret_cast<const char*>(s.data16);
-    q.scl = reinterpret_cast<const char*>(s.scl16);
-    q.offs = reinterpret_cast<const char*>(s.offs16);
-    if (in->wts) q.wts = reinterpret_cast<const char*>(s.wts16);
-  }
+  if (host && (rc = stage_i16(h, q, s.data16, s.scl16, s.offs16, s.wts16, n, in->npart, in->nsub,
+                              in->proflen, pfd_npol(pol))))
+    return rc;
   double* dout = host ? s.out : out;
   const int64_t dstride = host ? 1 : out_stride;
   const hipError_t e = pfe::launch_pfd_avgprof_i16(q, in->npart, in->nsub, in->proflen, n, s.csum,
@@ -1396,11 +1436,17 @@ int pfe_pfd_avgprof_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, in
   return pfd_avgprof_i16_call(h, in, out, out_stride, flags);
 }
 
+int pfe_pfd_avgprof_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                            double* out, int64_t out_stride, uint32_t flags) {
+  return pfd_avgprof_i16_call(h, in, out, out_stride, flags, true, pol);
+}
+
 // pfe_pfd_scrunch (xd), pfe_pfd_scrunch_f32 (xf) and pfe_pfd_scrunch_i16 (i16: the four arrays,
 // the strides and the shape of the caller's struct; the shape arguments are then its own)
 static int pfd_scrunch_call(pfe_handle* h, const char* fn, const double* xd, const float* xf,
                             bool f32, const pfe_pfd_i16_in* i16, int npart, int nchan, int nbin, int64_t n,
-                            const pfe_pfd_scrunch_how* how, double* out, uint32_t flags) {
+                            const pfe_pfd_scrunch_how* how, double* out, uint32_t flags,
+                            const pfe_pfd_i16_pol* pol = nullptr) {
   if (!h) return PFE_EINVAL;
   h->err.clear();
   if (!how || !out) return set_err(h, PFE_EINVAL, "%s: null argument", fn);
@@ -1419,7 +1465,7 @@ static int pfd_scrunch_call(pfe_handle* h, const char* fn, const double* xd, con
     return set_err(h, PFE_EINVAL, "%s: bscr %d does not divide nbin %d", fn, how->bscr, nbin);
   int rc;
   if (i16) {
-    if ((rc = pfd_i16_check(h, fn, i16, flags, false))) return rc;
+    if ((rc = pfd_i16_check(h, fn, i16, flags, false, pol))) return rc;
   } else {
     if (f32 ? !xf : !xd) return set_err(h, PFE_EINVAL, "%s: null input array", fn);
     if (f32 ? ((uintptr_t)xf & 3) : ((uintptr_t)xd & 7))
@@ -1435,7 +1481,7 @@ static int pfd_scrunch_call(pfe_handle* h, const char* fn, const double* xd, con
   pfe::PfdScrunchSrc x;
   x.f64 = xd;
   x.f32 = xf;
-  if (i16) x.i16 = pfe::pfd_i16_src(*i16, flags & PFE_FLAG_PFD_BSWAP);
+  if (i16) x.i16 = pfe::pfd_i16_src(*i16, flags & PFE_FLAG_PFD_BSWAP, pfd_npol(pol), pfd_nsum(pol));
   const int32_t* rot = how->rot;
   double* z = out;
   if (host) {
@@ -1444,19 +1490,13 @@ static int pfd_scrunch_call(pfe_handle* h, const char* fn, const double* xd, con
       return pfe::pfd_scrunch_layout(
           A, E, ES, nchan, GK, n, true, f32,
           !i16 ? pfe::PFD_I16_NONE : i16->wts ? pfe::PFD_I16_WEIGHTS : pfe::PFD_I16_PLAIN,
-          rot != nullptr);
+          rot != nullptr, pfd_nsum(pol));
     });
     if (rc) return rc;
     if (i16) {
-      if ((rc = stage_in(h, s.data16, i16->data, (size_t)n * E)) ||
-          (rc = stage_in(h, s.scl16, i16->scl, (size_t)n * ES)) ||
-          (rc = stage_in(h, s.offs16, i16->offs, (size_t)n * ES)) ||
-          (i16->wts && (rc = stage_in(h, s.wts16, i16->wts, (size_t)n * ES))))
+      if ((rc = stage_i16(h, x.i16, s.data16, s.scl16, s.offs16, s.wts16, n, npart, nchan, nbin,
+                          pfd_npol(pol))))
         return rc;
-      x.i16.data = reinterpret_cast<const char*>(s.data16);
-      x.i16.scl = reinterpret_cast<const char*>(s.scl16);
-      x.i16.offs = reinterpret_cast<const char*>(s.offs16);
-      if (i16->wts) x.i16.wts = reinterpret_cast<const char*>(s.wts16);
     } else if (f32) {
       if ((rc = stage_in(h, s.profs32, xf, (size_t)n * E))) return rc;
       x.f32 = s.profs32;
@@ -1504,6 +1544,17 @@ int pfe_pfd_scrunch_i16(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_s
                           in->n, how, out, flags);
 }
 
+int pfe_pfd_scrunch_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                            const pfe_pfd_scrunch_how* how, double* out, uint32_t flags) {
+  if (h && !in) {
+    h->err.clear();
+    return set_err(h, PFE_EINVAL, "pfd_scrunch_i16_pol: null argument");
+  }
+  if (!h) return PFE_EINVAL;
+  return pfd_scrunch_call(h, "pfd_scrunch_i16_pol", nullptr, nullptr, false, in, in->npart, in->nsub,
+                          in->proflen, in->n, how, out, flags, pol);
+}
+
 int pfe_pfd_dmprof_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* profile, float* chis,
                        double* lyon8, uint32_t* status, uint32_t flags) {
   if (h && !in) {
@@ -1512,6 +1563,18 @@ int pfe_pfd_dmprof_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* profile,
   }
   PfdI16View v(in, flags);
   return pfd_dmprof_call(h, v.view, false, nullptr, profile, chis, lyon8, status, flags, in, v.q);
+}
+
+int pfe_pfd_dmprof_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                           double* profile, float* chis, double* lyon8, uint32_t* status,
+                           uint32_t flags) {
+  if (h && !in) {
+    h->err.clear();
+    return set_err(h, PFE_EINVAL, "pfd_dmprof_i16_pol: null argument");
+  }
+  PfdI16View v(in, flags, pol);
+  return pfd_dmprof_call(h, v.view, false, nullptr, profile, chis, lyon8, status, flags, in, v.q, false,
+                         nullptr, true, pol);
 }
 
 int pfe_pfd_dmprof(pfe_handle* h, const pfe_pfd_in* in, double* profile, float* chis,
@@ -1548,7 +1611,8 @@ int pfe_pfd_dmprof_kill_f32(pfe_handle* h, const pfe_pfd_f32_in* in, const pfe_p
 static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const float* x32,
                            double* out, uint32_t* status, uint32_t flags, const char* fn,
                            unsigned groups, int c0, int k, const pfe_pfd_i16_in* i16 = nullptr,
-                           pfe::PfdI16Src* q = nullptr, const pfe_pfd_kill* kill = nullptr) {
+                           pfe::PfdI16Src* q = nullptr, const pfe_pfd_kill* kill = nullptr,
+                           const pfe_pfd_i16_pol* pol = nullptr) {
   int64_t n;
   int rc = call_check(h, fn, in, out && status, n);
   if (rc || n == 0) return rc;
@@ -1556,7 +1620,7 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   if (in->npart < 1 || in->nsub < 2 || in->proflen < 8 || in->proflen > 1024)
     return set_err(h, PFE_EINVAL, "%s: shape %dx%dx%d unsupported", fn, in->npart, in->nsub,
                    in->proflen);
-  if (q && (rc = pfd_i16_check(h, fn, i16, flags, true))) return rc;
+  if (q && (rc = pfd_i16_check(h, fn, i16, flags, true, pol))) return rc;
   const bool useg = pfd_use_global(h, in);
   if (useg && !pfe::pfd_global_plan(in->nsub, in->proflen, n).ok)
     return pfd_shape_err(h, fn, in);
@@ -1586,7 +1650,7 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
     return [&, cn](pfe::Arena& A) {
       return pfe::pfd_scores_layout(A, *in, host, groups, k, plan(cn).bytes(), cus, h->opt,
                                     sums ? pass : 0, cn, derive, be || (killed && !f32), ki,
-                                    kmask.mask());
+                                    kmask.mask(), pfd_nsum(pol));
     };
   };
   if (n % pass) {  // a shorter last pass: its layout fits as well
@@ -1596,7 +1660,7 @@ static int pfd_scores_call(pfe_handle* h, const pfe_pfd_in* in, bool f32, const 
   }
   pfe::PfdScoresStage s;
   rc = lay_out(h, s, walk(pass));
-  if (rc || (host && (rc = stage_pfd(h, in, x32, q, s.in, a)))) return rc;
+  if (rc || (host && (rc = stage_pfd(h, in, x32, q, s.in, a, pfd_npol(pol))))) return rc;
   if (host && killed && (rc = stage_kill(h, kmask, s.in.kparts, s.in.ksubs, n, in->npart, in->nsub)))
     return rc;
   double* wscal = nullptr;
@@ -1678,8 +1742,33 @@ static int pfd_scores_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, 
   return pfd_scores_call(h, v.view, false, nullptr, out, status, flags, fn.c_str(), c.groups, c.c0,
                          c.k, in, v.q);
 }
+// the _i16_pol forms: the texts under the _i16_pol name, the polarisations beside `in`
+static int pfd_scores_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                              double* out, uint32_t* status, uint32_t flags, const PfdScores& c) {
+  PfdI16View v(in, flags, pol);
+  const std::string fn = std::string(c.fn) + "_i16_pol";
+  return pfd_scores_call(h, v.view, false, nullptr, out, status, flags, fn.c_str(), c.groups, c.c0,
+                         c.k, in, v.q, nullptr, pol);
+}
 
 extern "C" {
+
+int pfe_pfd_bates22_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                            double* out, uint32_t* status, uint32_t flags) {
+  return pfd_scores_i16_pol(h, in, pol, out, status, flags, PFD_BATES22);
+}
+int pfe_pfd_params4_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                            double* out, uint32_t* status, uint32_t flags) {
+  return pfd_scores_i16_pol(h, in, pol, out, status, flags, PFD_PARAMS4);
+}
+int pfe_pfd_dmfit4_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                           double* out, uint32_t* status, uint32_t flags) {
+  return pfd_scores_i16_pol(h, in, pol, out, status, flags, PFD_DMFIT4);
+}
+int pfe_pfd_subband3_i16_pol(pfe_handle* h, const pfe_pfd_i16_in* in, const pfe_pfd_i16_pol* pol,
+                             double* out, uint32_t* status, uint32_t flags) {
+  return pfd_scores_i16_pol(h, in, pol, out, status, flags, PFD_SUBBAND3);
+}
 
 int pfe_pfd_bates22_i16(pfe_handle* h, const pfe_pfd_i16_in* in, double* out, uint32_t* status,
                         uint32_t flags) {

@@ -384,36 +384,58 @@ enum PfdI16 { PFD_I16_NONE = 0, PFD_I16_PLAIN = 1, PFD_I16_WEIGHTS = 2 };
 // the four arrays of an int16 call as the kernels read them: value (c, p, s, b) of data at
 // data + c*dfs + p*dps + 2*(s*L + b), value (c, p, s) of scl (offs, wts) at scl + c*pfs +
 // p*pps + 4*s.  Dense arrays have the strides of their shapes; table rows share one pair
+//
+// A cube with a polarisation axis (the _i16_pol calls: npol stored per (fold, part), dense between
+// part and sub-band in data, scl and offs; wts has none): polarisation k of a value lies dks (of
+// its scl and offs: pks) bytes further, the leading nsum of them are summed, and value (c, p, s)
+// of wts is at wts + c*wfs + p*wps + 4*s.  Table rows still share one pair of strides; dense
+// arrays of npol > 1 do not (wfs != pfs).  pfd_i16_ns() says which kernels read the cube
 struct PfdI16Src {
   const char *data = nullptr, *scl = nullptr, *offs = nullptr, *wts = nullptr;  // wts may be null
   int64_t dfs = 0, dps = 0, pfs = 0, pps = 0;  // bytes
   bool bswap = false;                          // PFE_FLAG_PFD_BSWAP: every value byte-reversed
+  int nsum = 1;                                // polarisations summed: 1 or 2
+  int64_t dks = 0, pks = 0;                    // bytes between polarisations: data, scl / offs
+  int64_t wfs = 0, wps = 0;                    // bytes between folds and parts of wts
   PfdI16Src from(int64_t c0) const {           // folds c0 ..
     PfdI16Src r = *this;
     r.data += c0 * dfs;
     r.scl += c0 * pfs;
     r.offs += c0 * pfs;
-    if (wts) r.wts += c0 * pfs;
+    if (wts) r.wts += c0 * wfs;
     return r;
   }
 };
-inline PfdI16Src pfd_i16_src(const pfe_pfd_i16_in& in, bool bswap) {
+// npol polarisations stored, the leading nsum summed (1, 1: the cube of the _i16 calls)
+inline PfdI16Src pfd_i16_src(const pfe_pfd_i16_in& in, bool bswap, int npol = 1, int nsum = 1) {
   PfdI16Src q;
   q.data = reinterpret_cast<const char*>(in.data);
   q.scl = reinterpret_cast<const char*>(in.scl);
   q.offs = reinterpret_cast<const char*>(in.offs);
   q.wts = reinterpret_cast<const char*>(in.wts);
+  q.dks = (int64_t)2 * in.nsub * in.proflen;
+  q.pks = (int64_t)4 * in.nsub;
   if (in.fold_stride) {
-    q.dfs = q.pfs = in.fold_stride;
-    q.dps = q.pps = in.part_stride;
+    q.dfs = q.pfs = q.wfs = in.fold_stride;
+    q.dps = q.pps = q.wps = in.part_stride;
   } else {
-    q.dps = (int64_t)2 * in.nsub * in.proflen;
+    q.dps = q.dks * npol;
     q.dfs = q.dps * in.npart;
-    q.pps = (int64_t)4 * in.nsub;
+    q.pps = q.pks * npol;
     q.pfs = q.pps * in.npart;
+    q.wps = q.pks;
+    q.wfs = q.wps * in.npart;
   }
+  q.nsum = nsum;
   q.bswap = bswap;
   return q;
+}
+// the NS of the kernels that read x (pfd_i16_dev.h): 0, the kernels of the _i16 calls, whenever
+// one polarisation is read and the weights lie where those kernels look for them (none given, or
+// the strides of scl: table rows, and dense arrays of npol = 1); else the polarisations read
+inline int pfd_i16_ns(const PfdI16Src& x) {
+  if (x.nsum == 2) return 2;
+  return x.wts && (x.wfs != x.pfs || x.wps != x.pps) ? 1 : 0;
 }
 // s[c][e] = x(c,0,e) + ... + x(c,npart-1,e), x the decoded value ((double)d * scl + offs, then
 // * wts when given), e over nsub x L, c over n folds; s dense
@@ -486,7 +508,8 @@ hipError_t launch_pfd_scrunch(const PfdScrunchSrc& x, const int32_t* rot, double
 // pfe_pfd_scrunch / _f32 / _i16: a host-pointer call stages the cube as the values it holds (an
 // int16 cube with scl, offs and, when given, wts behind it: ES = npart x nchan floats a fold
 // each), then rot (n x nchan, when given), then out (n x GK doubles, GK = G x K).  A
-// device-pointer call takes no scratch
+// device-pointer call takes no scratch.  pol (a _i16_pol call: the polarisations it sums): the
+// cube, scl and offs staged compacted, pol times their size, the axis between part and channel
 struct PfdScrunchStage {
   double* profs = nullptr;
   float* profs32 = nullptr;
@@ -496,13 +519,14 @@ struct PfdScrunchStage {
   double* out = nullptr;
 };
 inline PfdScrunchStage pfd_scrunch_layout(Arena& A, int64_t E, int64_t ES, int nchan, int64_t GK,
-                                          int64_t n, bool host, bool f32, int i16, bool rot) {
+                                          int64_t n, bool host, bool f32, int i16, bool rot,
+                                          int pol = 1) {
   PfdScrunchStage s;
   if (!host) return s;
   if (i16) {
-    s.data16 = A.take<int16_t>((size_t)n * E, "data16");
-    s.scl16 = A.take<float>((size_t)n * ES, "scl16");
-    s.offs16 = A.take<float>((size_t)n * ES, "offs16");
+    s.data16 = A.take<int16_t>((size_t)n * E * pol, "data16");
+    s.scl16 = A.take<float>((size_t)n * ES * pol, "scl16");
+    s.offs16 = A.take<float>((size_t)n * ES * pol, "offs16");
     if (i16 == PFD_I16_WEIGHTS) s.wts16 = A.take<float>((size_t)n * ES, "wts16");
   } else if (f32)
     s.profs32 = A.take<float>((size_t)n * E, "profs32");
@@ -539,7 +563,9 @@ hipError_t launch_pfd_avgprof_kill(const void* x, int elem, const PfdKillSrc& k,
 
 // pfe_pfd_avgprof / pfe_pfd_avgprof_f32: a host-pointer call stages the cube (as the values it
 // holds) and its n results; the chunk sums follow.  A masked call (kill: PfdKillMask bits, with
-// the fold's npart and nsub) stages its masks directly behind the cube, parts then subs
+// the fold's npart and nsub) stages its masks directly behind the cube, parts then subs.  pol (a
+// _i16_pol call: the polarisations it sums): data16, scl16 and offs16 pol times their size; E
+// stays the npart x nsub x proflen summed values of a fold
 struct PfdAvgStage {
   double* profs = nullptr;
   float* profs32 = nullptr;
@@ -550,13 +576,13 @@ struct PfdAvgStage {
 };
 inline PfdAvgStage pfd_avgprof_layout(Arena& A, int64_t E, int64_t n, bool host, bool f32,
                                       int i16 = PFD_I16_NONE, int64_t ES = 0, int kill = 0,
-                                      int npart = 0, int nsub = 0) {
+                                      int npart = 0, int nsub = 0, int pol = 1) {
   PfdAvgStage s;
   if (host) {
     if (i16) {
-      s.data16 = A.take<int16_t>((size_t)n * E, "data16");
-      s.scl16 = A.take<float>((size_t)n * ES, "scl16");
-      s.offs16 = A.take<float>((size_t)n * ES, "offs16");
+      s.data16 = A.take<int16_t>((size_t)n * E * pol, "data16");
+      s.scl16 = A.take<float>((size_t)n * ES * pol, "scl16");
+      s.offs16 = A.take<float>((size_t)n * ES * pol, "offs16");
       if (i16 == PFD_I16_WEIGHTS) s.wts16 = A.take<float>((size_t)n * ES, "wts16");
     } else if (f32)
       s.profs32 = A.take<float>((size_t)n * E, "profs32");
@@ -588,7 +614,9 @@ inline PfdAvgWork pfd_avg_work_layout(Arena& A, const pfe_pfd_in& in, bool host,
 // the three inputs every PFD call stages.  A float32 call (f32_chunk > 0: its folds per pass)
 // stages the cube as the floats it is (profs32, no profs), and -- host pointers or device --
 // takes psum behind its staged arrays.  A masked call (kill: PfdKillMask bits) stages its masks
-// directly behind scal, parts then subs, each only when given
+// directly behind scal, parts then subs, each only when given.  pol (a _i16_pol call: the
+// polarisations it sums, staged compacted): data16, scl16 and offs16 pol times their size; wts16
+// has no polarisation axis
 struct PfdInputs {
   double *profs = nullptr, *subfreqs = nullptr, *scal = nullptr;
   float* profs32 = nullptr;
@@ -598,14 +626,14 @@ struct PfdInputs {
   double* psum = nullptr;
 };
 inline PfdInputs pfd_inputs_layout(Arena& A, const pfe_pfd_in& in, bool f32 = false,
-                                   int i16 = PFD_I16_NONE, int kill = 0) {
+                                   int i16 = PFD_I16_NONE, int kill = 0, int pol = 1) {
   PfdInputs s;
   const size_t n = (size_t)in.n, cube = n * in.npart * in.nsub * in.proflen;
   if (i16) {
     const size_t par = n * in.npart * in.nsub;
-    s.data16 = A.take<int16_t>(cube, "data16");
-    s.scl16 = A.take<float>(par, "scl16");
-    s.offs16 = A.take<float>(par, "offs16");
+    s.data16 = A.take<int16_t>(cube * pol, "data16");
+    s.scl16 = A.take<float>(par * pol, "scl16");
+    s.offs16 = A.take<float>(par * pol, "offs16");
     if (i16 == PFD_I16_WEIGHTS) s.wts16 = A.take<float>(par, "wts16");
   } else if (f32)
     s.profs32 = A.take<float>(cube, "profs32");
@@ -642,11 +670,11 @@ inline PfdDmprofStage pfd_dmprof_layout(Arena& A, const pfe_pfd_in& in, bool hos
                                         bool chis, bool lyon8, size_t ws_bytes,
                                         int64_t f32_chunk = 0, bool avgprof = false,
                                         bool be64 = false, int i16 = PFD_I16_NONE,
-                                        int kill = 0) {
+                                        int kill = 0, int pol = 1) {
   PfdDmprofStage s;
   const size_t n = (size_t)in.n;
   if (host) {
-    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64, i16, kill);
+    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64, i16, kill, pol);
     if (profile) s.profile = A.take<double>(n * in.proflen, "profile");
     if (chis) s.chis = A.take<float>(n * PFE_PFD_NDM, "chis");
     if (lyon8) s.lyon8 = A.take<double>(n * 8, "lyon8");
@@ -682,12 +710,12 @@ inline PfdScoresStage pfd_scores_layout(Arena& A, const pfe_pfd_in& in, bool hos
                                         const Options& o, int64_t f32_chunk = 0,
                                         int64_t pass = 0, bool avgprof = false,
                                         bool be64 = false, int i16 = PFD_I16_NONE,
-                                        int kill = 0) {
+                                        int kill = 0, int pol = 1) {
   PfdScoresStage s;
   const size_t n = (size_t)in.n;
   const int64_t wn = f32_chunk > 0 ? pass : in.n;
   if (host) {
-    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64, i16, kill);
+    s.in = pfd_inputs_layout(A, in, f32_chunk > 0 && !be64, i16, kill, pol);
     s.out = A.take<double>(n * k, "out");
     s.status = A.take<uint32_t>(n, "status");
   }

@@ -97,9 +97,66 @@ struct i16_cursor {
     return v;
   }
 };
-// the int16 cube of a launch: what a `const T* X` is for the others
+// the int16 cube of a launch: what a `const T* X` is for the others.  It carries the arrays and
+// the four strides these kernels read and nothing of the polarisation fields PfdI16Src has
+// beside them, so the kernels' arguments, and with them their code, are what they were
+struct i16_arrays {
+  const char *data, *scl, *offs, *wts;
+  int64_t dfs, dps, pfs, pps;
+  bool bswap;
+  explicit i16_arrays(const PfdI16Src& q)
+      : data(q.data), scl(q.scl), offs(q.offs), wts(q.wts), dfs(q.dfs), dps(q.dps), pfs(q.pfs),
+        pps(q.pps), bswap(q.bswap) {}
+};
 template <bool BS, bool WT>
 struct i16_cube {
+  i16_arrays x;
+  unsigned E1, L;
+};
+
+// A value of an int16 cube with a polarisation axis (the _i16_pol calls; NS = 1, 2 as in
+// pfd_i16_dev.h) as loaded: the NS polarisations of one (part, sub-band, bin) with their scales and
+// offsets and the one weight.  Its value is the polarisation sum: each decoded with one rounding,
+// y_0 + y_1 rounded once, then, WT, the sum times the weight rounded once
+template <bool BS, bool WT, int NS>
+struct i16_pol_elem {
+  unsigned d[NS], a[NS], o[NS], w;
+  __device__ __forceinline__ explicit operator double() const {
+    double x = (double)i16_elem<BS, false>{d[0], a[0], o[0], 0u};
+    if constexpr (NS == 2) x = x + (double)i16_elem<BS, false>{d[1], a[1], o[1], 0u};
+    if constexpr (WT) return x * i16_elem<BS, false>::f32(w);
+    return x;
+  }
+};
+// i16_cursor for such a cube.  The 32-bit part of the walk is as there (r + k < 2^31: j, p and e
+// fit); the polarisation strides and the weights' own part stride are added in 64 bits, to
+// pointers, so they put no bound of their own on the shape
+template <bool BS, bool WT, int NS>
+struct i16_pol_cursor {
+  const char *data, *scl, *offs, *wts;  // of the fold's part p0, polarisation 0
+  int64_t dps, pps, wps, dks, pks;
+  unsigned E1, L, r;
+  __device__ __forceinline__ i16_pol_cursor operator+(int k) const {
+    i16_pol_cursor c = *this;
+    c.r += (unsigned)k;
+    return c;
+  }
+  __device__ __forceinline__ i16_pol_elem<BS, WT, NS> operator[](int k) const {
+    const unsigned j = r + (unsigned)k, p = j / E1, e = j - p * E1;
+    const int64_t sb = (int64_t)4 * (e / L), at = (int64_t)p * pps + sb;
+    i16_pol_elem<BS, WT, NS> v;
+#pragma unroll
+    for (int m = 0; m < NS; ++m) {
+      v.d[m] = *reinterpret_cast<const unsigned short*>(data + (int64_t)p * dps + m * dks + (int64_t)2 * e);
+      v.a[m] = *reinterpret_cast<const unsigned*>(scl + at + m * pks);
+      v.o[m] = *reinterpret_cast<const unsigned*>(offs + at + m * pks);
+    }
+    v.w = WT ? *reinterpret_cast<const unsigned*>(wts + (int64_t)p * wps + sb) : 0u;
+    return v;
+  }
+};
+template <bool BS, bool WT, int NS>
+struct i16_pol_cube {
   PfdI16Src x;
   unsigned E1, L;
 };
@@ -158,6 +215,26 @@ __device__ __forceinline__ i16_cursor<BS, WT> avg_at(const i16_cube<BS, WT>& X, 
   c.wts = WT ? X.x.wts + fold * X.x.pfs + p0 * X.x.pps : nullptr;
   c.dps = X.x.dps;
   c.pps = X.x.pps;
+  c.E1 = X.E1;
+  c.L = X.L;
+  c.r = (unsigned)(e0 - p0 * X.E1);
+  return c;
+}
+
+template <bool BS, bool WT, int NS>
+__device__ __forceinline__ i16_pol_cursor<BS, WT, NS> avg_at(const i16_pol_cube<BS, WT, NS>& X,
+                                                              int64_t fold, int64_t, int64_t e0) {
+  const int64_t p0 = e0 / X.E1;
+  i16_pol_cursor<BS, WT, NS> c;
+  c.data = X.x.data + fold * X.x.dfs + p0 * X.x.dps;
+  c.scl = X.x.scl + fold * X.x.pfs + p0 * X.x.pps;
+  c.offs = X.x.offs + fold * X.x.pfs + p0 * X.x.pps;
+  c.wts = WT ? X.x.wts + fold * X.x.wfs + p0 * X.x.wps : nullptr;
+  c.dps = X.x.dps;
+  c.pps = X.x.pps;
+  c.wps = X.x.wps;
+  c.dks = X.x.dks;
+  c.pks = X.x.pks;
   c.E1 = X.E1;
   c.L = X.L;
   c.r = (unsigned)(e0 - p0 * X.E1);
@@ -359,13 +436,23 @@ hipError_t launch_pfd_avgprof_be64(const double* x, int64_t E, int L, int64_t n,
 template <bool BS>
 static hipError_t launch_avgprof_i16(const PfdI16Src& x, unsigned E1, int64_t E, int L, int64_t n,
                                      double* csum, double* out, int64_t stride, hipStream_t st) {
-  if (x.wts) return launch_avgprof(i16_cube<BS, true>{x, E1, (unsigned)L}, E, L, n, csum, out, stride, st);
-  return launch_avgprof(i16_cube<BS, false>{x, E1, (unsigned)L}, E, L, n, csum, out, stride, st);
+  const int ns = pfd_i16_ns(x);
+  if (ns == 2) {
+    if (x.wts)
+      return launch_avgprof(i16_pol_cube<BS, true, 2>{x, E1, (unsigned)L}, E, L, n, csum, out, stride, st);
+    return launch_avgprof(i16_pol_cube<BS, false, 2>{x, E1, (unsigned)L}, E, L, n, csum, out, stride, st);
+  }
+  if (ns == 1)  // one polarisation of several, its weights (given) apart from scl's strides
+    return launch_avgprof(i16_pol_cube<BS, true, 1>{x, E1, (unsigned)L}, E, L, n, csum, out, stride, st);
+  const i16_arrays a(x);
+  if (x.wts) return launch_avgprof(i16_cube<BS, true>{a, E1, (unsigned)L}, E, L, n, csum, out, stride, st);
+  return launch_avgprof(i16_cube<BS, false>{a, E1, (unsigned)L}, E, L, n, csum, out, stride, st);
 }
 hipError_t launch_pfd_avgprof_i16(const PfdI16Src& x, int npart, int nsub, int L, int64_t n,
                                   double* csum, double* out, int64_t stride, hipStream_t st) {
   const int64_t E1 = (int64_t)nsub * L, E = E1 * npart;
-  if (E1 < 1 || E1 > 0x7fffffff - PFD_AVG_CHUNK) return hipErrorInvalidValue;  // i16_cursor's 32 bits
+  // i16_cursor's and i16_pol_cursor's 32 bits (the polarisation strides are 64-bit offsets)
+  if (E1 < 1 || E1 > 0x7fffffff - PFD_AVG_CHUNK) return hipErrorInvalidValue;
   return x.bswap ? launch_avgprof_i16<true>(x, (unsigned)E1, E, L, n, csum, out, stride, st)
                  : launch_avgprof_i16<false>(x, (unsigned)E1, E, L, n, csum, out, stride, st);
 }

@@ -36,7 +36,10 @@ constexpr int PSUM_BURST = 8;  // part loads a lane keeps in flight
 // bins: a lane whose four elements lie in one sub-band -- all but the lanes on a seam -- loads
 // them once per part (neighbouring lanes read the same words: one cache line a wave), a lane
 // on a seam loads them per element.  Same operations, same bits on every path.
-template <bool VEC, bool BS, bool WT>
+// NS (pfd_i16_dev.h; 0: the cube of the _i16 calls): x the sum of NS polarisations, weighted once
+// -- a burst step loads both polarisations of 4 parts, a seam step both of one.  The condition of
+// the 8-byte loads is the same: E % 4 == 0 makes the polarisation stride 2 E a multiple of 8.
+template <bool VEC, bool BS, bool WT, int NS = 0>
 __global__ __launch_bounds__(PSUM_THREADS) void k_pfd_partsum_i16(const PfdI16Src x,
                                                                   double* __restrict__ S, int NP,
                                                                   int L, int64_t E, int64_t total) {
@@ -59,7 +62,24 @@ __global__ __launch_bounds__(PSUM_THREADS) void k_pfd_partsum_i16(const PfdI16Sr
     par[u] = ok[u] ? c * x.pfs + (int64_t)4 * (e / L) : par[0];
   }
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  if (par[1] == par[0] && par[2] == par[0] && par[3] == par[0]) {
+  if constexpr (NS > 0) {
+    // the weights' own strides: the fold and the sub-band of each element once more
+    int64_t wpar[4];
+    int64_t wc = f / E;
+    int we = (int)(f - wc * E);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (u > 0 && ++we == (int)E) {
+        we = 0;
+        ++wc;
+      }
+      wpar[u] = ok[u] ? wc * x.wfs + (int64_t)4 * (we / L) : wpar[0];
+    }
+    if (par[1] == par[0] && par[2] == par[0] && par[3] == par[0])
+      psum_pol_run<VEC, BS, WT, NS>(x, q, par[0], wpar[0], NP, acc);
+    else
+      psum_pol_seam<VEC, BS, WT, NS>(x, q, par, wpar, NP, acc);
+  } else if (par[1] == par[0] && par[2] == par[0] && par[3] == par[0]) {
     int p = 0;
     for (; p + PSUM_BURST <= NP; p += PSUM_BURST)
       psum_add<VEC, BS, WT, PSUM_BURST>(x, q, par[0], p, acc);
@@ -98,7 +118,14 @@ __global__ __launch_bounds__(PSUM_THREADS) void k_pfd_partsum_i16(const PfdI16Sr
 template <bool VEC, bool BS>
 static void launch_psum(bool wt, dim3 grid, dim3 block, hipStream_t st, const PfdI16Src& x, double* s,
                         int npart, int L, int64_t E, int64_t total) {
-  if (wt)
+  const int ns = pfd_i16_ns(x);
+  if (ns == 2 && wt)
+    hipLaunchKernelGGL((k_pfd_partsum_i16<VEC, BS, true, 2>), grid, block, 0, st, x, s, npart, L, E, total);
+  else if (ns == 2)
+    hipLaunchKernelGGL((k_pfd_partsum_i16<VEC, BS, false, 2>), grid, block, 0, st, x, s, npart, L, E, total);
+  else if (ns == 1)  // one polarisation of several, its weights (given) apart from scl's strides
+    hipLaunchKernelGGL((k_pfd_partsum_i16<VEC, BS, true, 1>), grid, block, 0, st, x, s, npart, L, E, total);
+  else if (wt)
     hipLaunchKernelGGL((k_pfd_partsum_i16<VEC, BS, true>), grid, block, 0, st, x, s, npart, L, E, total);
   else
     hipLaunchKernelGGL((k_pfd_partsum_i16<VEC, BS, false>), grid, block, 0, st, x, s, npart, L, E, total);

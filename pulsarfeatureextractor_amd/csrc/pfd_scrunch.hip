@@ -87,7 +87,7 @@ __device__ __forceinline__ void scr_add(const T* const (&q)[4], int64_t ps, int 
 }
 // the part sums of values [e, e + 4) of the slab that begins at channel chan0 of fold `fold`;
 // values at or past `elems` are not there (their loads go to the quad's first value)
-template <class T, bool VEC, bool BS, bool WT>
+template <class T, bool VEC, bool BS, bool WT, int NS>
 __device__ __forceinline__ void scr_quad(const ScrDense<T>& x, int64_t fold, int64_t chan0, int e,
                                          int elems, int nbin, int NP, double (&acc)[4]) {
   const T* q[4];
@@ -107,7 +107,7 @@ __device__ __forceinline__ void scr_quad(const ScrDense<T>& x, int64_t fold, int
   if (p < NP) scr_add<T, VEC, 1>(q, x.ps, p, acc);
 }
 // the part sum of one value: channel `chan`, bin b
-template <class T, bool BS, bool WT>
+template <class T, bool BS, bool WT, int NS>
 __device__ __forceinline__ double scr_one(const ScrDense<T>& x, int64_t fold, int64_t chan, int b,
                                           int nbin, int NP) {
   const T* q = x.x + fold * x.fs + chan * nbin + b;
@@ -128,7 +128,9 @@ __device__ __forceinline__ double scr_one(const ScrDense<T>& x, int64_t fold, in
 }
 
 // ---- int16 cubes: the decode and the bursts of pfd_i16_dev.h -------------------------------
-template <class T, bool VEC, bool BS, bool WT>
+// NS (pfd_i16_dev.h; 0: the cube of the _i16 calls): a value is the sum of NS polarisations,
+// weighted once; the same helpers on both routes, so the same bits
+template <class T, bool VEC, bool BS, bool WT, int NS>
 __device__ __forceinline__ void scr_quad(const PfdI16Src& x, int64_t fold, int64_t chan0, int e,
                                          int elems, int nbin, int NP, double (&acc)[4]) {
   const char* q[4];
@@ -146,7 +148,18 @@ __device__ __forceinline__ void scr_quad(const PfdI16Src& x, int64_t fold, int64
     q[u] = ok ? q[0] + 2 * u : q[0];
     par[u] = ok ? fold * x.pfs + (int64_t)4 * (chan0 + cc) : par[0];
   }
-  if (par[1] == par[0] && par[2] == par[0] && par[3] == par[0]) {
+  if constexpr (NS > 0) {
+    int64_t wpar[4];  // the weights have strides of their own
+#pragma unroll
+    for (int u = 0; u < 4; ++u) wpar[u] = par[u] - fold * x.pfs + fold * x.wfs;
+    // a block of 1024 lanes has 128 registers a lane: the 2-byte loads of two polarisations
+    // (four a part and polarisation) go two parts at a time, 16 loads in flight, to stay in them
+    constexpr int B = NS == 2 && !VEC ? 2 : 8 / NS;
+    if (par[1] == par[0] && par[2] == par[0] && par[3] == par[0])
+      psum_pol_run<VEC, BS, WT, NS, B>(x, q, par[0], wpar[0], NP, acc);
+    else
+      psum_pol_seam<VEC, BS, WT, NS>(x, q, par, wpar, NP, acc);
+  } else if (par[1] == par[0] && par[2] == par[0] && par[3] == par[0]) {
     int p = 0;
     for (; p + SCR_BURST <= NP; p += SCR_BURST) psum_add<VEC, BS, WT, SCR_BURST>(x, q, par[0], p, acc);
     if (p + 4 <= NP) {
@@ -171,33 +184,41 @@ __device__ __forceinline__ void scr_quad(const PfdI16Src& x, int64_t fold, int64
     }
   }
 }
-template <class T, bool BS, bool WT>
+template <class T, bool BS, bool WT, int NS>
 __device__ __forceinline__ double scr_one(const PfdI16Src& x, int64_t fold, int64_t chan, int b,
                                           int nbin, int NP) {
   const char* q = x.data + fold * x.dfs + (int64_t)2 * (chan * nbin + b);
   const int64_t par = fold * x.pfs + (int64_t)4 * chan;
   double acc = 0.0;
   int p = 0;
-  for (; p + 4 <= NP; p += 4) {
-    unsigned short v[4];
-    I16Par r[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      v[u] = __builtin_nontemporal_load(
-          reinterpret_cast<const unsigned short*>(q + (int64_t)(p + u) * x.dps));
-      r[u] = i16_par<WT>(x, par + (int64_t)(p + u) * x.pps);
+  if constexpr (NS > 0) {
+    const int64_t wpar = fold * x.wfs + (int64_t)4 * chan;
+    for (; p < NP; ++p) {
+      const double y = i16_pol_one<BS, WT, NS>(x, q, par, wpar, p);
+      acc = p == 0 ? y : acc + y;
     }
+  } else {
+    for (; p + 4 <= NP; p += 4) {
+      unsigned short v[4];
+      I16Par r[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const double y = i16_decode<BS, WT>(i16_value<BS>(v[u]), r[u]);
-      acc = u == 0 && p == 0 ? y : acc + y;
+      for (int u = 0; u < 4; ++u) {
+        v[u] = __builtin_nontemporal_load(
+            reinterpret_cast<const unsigned short*>(q + (int64_t)(p + u) * x.dps));
+        r[u] = i16_par<WT>(x, par + (int64_t)(p + u) * x.pps);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const double y = i16_decode<BS, WT>(i16_value<BS>(v[u]), r[u]);
+        acc = u == 0 && p == 0 ? y : acc + y;
+      }
     }
-  }
-  for (; p < NP; ++p) {
-    const unsigned short v =
-        __builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(q + (int64_t)p * x.dps));
-    const double y = i16_decode<BS, WT>(i16_value<BS>(v), i16_par<WT>(x, par + (int64_t)p * x.pps));
-    acc = p == 0 ? y : acc + y;
+    for (; p < NP; ++p) {
+      const unsigned short v =
+          __builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(q + (int64_t)p * x.dps));
+      const double y = i16_decode<BS, WT>(i16_value<BS>(v), i16_par<WT>(x, par + (int64_t)p * x.pps));
+      acc = p == 0 ? y : acc + y;
+    }
   }
   return acc;
 }
@@ -211,7 +232,7 @@ __device__ __forceinline__ double scr_one(const PfdI16Src& x, int64_t fold, int6
 // part and lies in one channel; else every value is loaded alone and a quad may span two
 // channels, or end past the slab.  An output lane owns the same k in every slab, so the running
 // sums need no barrier of their own; the slab is fenced on both sides.
-template <class T, bool VEC, bool BS, bool WT>
+template <class T, bool VEC, bool BS, bool WT, int NS = 0>
 __global__ __launch_bounds__(SCR_MAX_THREADS) void k_pfd_scrunch(const ScrSrc<T> x,
                                                              const int32_t* __restrict__ rot,
                                                              double* __restrict__ Z, int NP, int nchan,
@@ -232,7 +253,7 @@ __global__ __launch_bounds__(SCR_MAX_THREADS) void k_pfd_scrunch(const ScrSrc<T>
     if (c0 > 0) __syncthreads();  // the last slab's readers are done
     for (int e = 4 * tid; e < elems; e += 4 * lanes) {
       double acc[4] = {0.0, 0.0, 0.0, 0.0};
-      scr_quad<T, VEC, BS, WT>(x, fold, chan0, e, elems, nbin, NP, acc);
+      scr_quad<T, VEC, BS, WT, NS>(x, fold, chan0, e, elems, nbin, NP, acc);
       if (VEC || e + 3 < elems) {
         f64x2* o = reinterpret_cast<f64x2*>(slab + e);
         o[0] = f64x2{acc[0], acc[1]};
@@ -269,7 +290,7 @@ __global__ __launch_bounds__(SCR_MAX_THREADS) void k_pfd_scrunch(const ScrSrc<T>
 // ---- the direct route ---------------------------------------------------------------------
 // A grid of n x G x tiles blocks, tile = SCR_THREADS output bins; lane k walks its fscr channels
 // and bscr bins in order and part-sums each value where it lies
-template <class T, bool BS, bool WT>
+template <class T, bool BS, bool WT, int NS = 0>
 __global__ __launch_bounds__(SCR_THREADS) void k_pfd_scrunch_direct(const ScrSrc<T> x,
                                                                     const int32_t* __restrict__ rot,
                                                                     double* __restrict__ Z, int NP,
@@ -288,7 +309,7 @@ __global__ __launch_bounds__(SCR_THREADS) void k_pfd_scrunch_direct(const ScrSrc
     if (b >= nbin) b -= nbin;
     double B = 0.0;
     for (int j = 0; j < bscr; ++j) {
-      const double s = scr_one<T, BS, WT>(x, fold, chan0 + cc, (int)b, nbin, NP);
+      const double s = scr_one<T, BS, WT, NS>(x, fold, chan0 + cc, (int)b, nbin, NP);
       B = j == 0 ? s : B + s;
       if (++b == nbin) b = 0;
     }
@@ -303,7 +324,7 @@ struct ScrShape {
   int64_t n;
 };
 
-template <class T, bool BS, bool WT>
+template <class T, bool BS, bool WT, int NS = 0>
 static hipError_t scr_launch(const ScrSrc<T>& x, bool vec, const int32_t* rot, double* z,
                              const ScrShape& s, bool direct, hipStream_t st) {
   const int G = s.nchan / s.fscr, K = s.nbin / s.bscr;
@@ -313,7 +334,7 @@ static hipError_t scr_launch(const ScrSrc<T>& x, bool vec, const int32_t* rot, d
     const int64_t blocks = s.n * G * tiles;
     for (int64_t b0 = 0; b0 < blocks; b0 += SCR_MAX_GRID) {
       const int64_t nb = blocks - b0 < SCR_MAX_GRID ? blocks - b0 : SCR_MAX_GRID;
-      hipLaunchKernelGGL((k_pfd_scrunch_direct<T, BS, WT>), dim3((unsigned)nb), block, 0, st, x, rot, z,
+      hipLaunchKernelGGL((k_pfd_scrunch_direct<T, BS, WT, NS>), dim3((unsigned)nb), block, 0, st, x, rot, z,
                          s.npart, s.nchan, s.nbin, s.fscr, s.bscr, (int)tiles, b0);
     }
     return hipGetLastError();
@@ -327,10 +348,10 @@ static hipError_t scr_launch(const ScrSrc<T>& x, bool vec, const int32_t* rot, d
   for (int64_t b0 = 0; b0 < blocks; b0 += SCR_MAX_GRID) {
     const dim3 grid((unsigned)(blocks - b0 < SCR_MAX_GRID ? blocks - b0 : SCR_MAX_GRID));
     if (vec)
-      hipLaunchKernelGGL((k_pfd_scrunch<T, true, BS, WT>), grid, block, lds, st, x, rot, z, s.npart,
+      hipLaunchKernelGGL((k_pfd_scrunch<T, true, BS, WT, NS>), grid, block, lds, st, x, rot, z, s.npart,
                          s.nchan, s.nbin, s.fscr, s.bscr, C, G, b0);
     else
-      hipLaunchKernelGGL((k_pfd_scrunch<T, false, BS, WT>), grid, block, lds, st, x, rot, z, s.npart,
+      hipLaunchKernelGGL((k_pfd_scrunch<T, false, BS, WT, NS>), grid, block, lds, st, x, rot, z, s.npart,
                          s.nchan, s.nbin, s.fscr, s.bscr, C, G, b0);
   }
   return hipGetLastError();
@@ -354,6 +375,17 @@ hipError_t launch_pfd_scrunch(const PfdScrunchSrc& x, const int32_t* rot, double
   }
   const PfdI16Src& q = x.i16;
   const bool vec = nbin % 4 == 0 && (((uintptr_t)q.data | (uintptr_t)q.dfs | (uintptr_t)q.dps) & 7) == 0;
+  const int ns = pfd_i16_ns(q);
+  if (ns == 2) {
+    if (q.bswap)
+      return q.wts ? scr_launch<int16_t, true, true, 2>(q, vec, rot, z, s, direct, st)
+                   : scr_launch<int16_t, true, false, 2>(q, vec, rot, z, s, direct, st);
+    return q.wts ? scr_launch<int16_t, false, true, 2>(q, vec, rot, z, s, direct, st)
+                 : scr_launch<int16_t, false, false, 2>(q, vec, rot, z, s, direct, st);
+  }
+  if (ns == 1)  // one polarisation of several, its weights (given) apart from scl's strides
+    return q.bswap ? scr_launch<int16_t, true, true, 1>(q, vec, rot, z, s, direct, st)
+                   : scr_launch<int16_t, false, true, 1>(q, vec, rot, z, s, direct, st);
   if (q.bswap)
     return q.wts ? scr_launch<int16_t, true, true>(q, vec, rot, z, s, direct, st)
                  : scr_launch<int16_t, true, false>(q, vec, rot, z, s, direct, st);
